@@ -56,7 +56,35 @@ def parse():
     ap.add_argument("--steady-steps", type=int, default=200)
     ap.add_argument("--persistent-obs", action="store_true", help="level5 family: te_set_persistent_obs (the stacked observation is updated in place: the caller passes the same buffer every step)")
     ap.add_argument("--own-stream", action="store_true", help="drive te_step from a stream of the bench's own instead of torch's current (null) stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline window, write what its last step returned as DIR/<name>.npy (rank 0's shard; a fixed sample "
+                         "of env rows when the arrays exceed the dump budget)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60 * 10**6   # the .npy files of --dump-outputs stay under 64 MB together (headers included)
+
+
+def dump_outputs(out_dir: str, outputs: dict, env_index_base: int = 0, seed: int = 0) -> list:
+    """Write `outputs` (name -> tensor whose first axis is the env) to out_dir/<name>.npy: floating tensors as float32, integer and
+    flag tensors as float64 (exact).  When every row would not fit in DUMP_BYTES, the same fixed, seeded sample of env rows is taken
+    from each tensor; env_index.npy holds the global index of every row written.  Returns the paths written."""
+    import torch
+    n = next(iter(outputs.values())).shape[0]
+    row_bytes = 8 + sum(t[0].numel() * (4 if t.is_floating_point() else 8) for t in outputs.values())
+    rows = min(n, DUMP_BYTES // row_bytes)
+    idx = np.arange(n) if rows == n else np.sort(np.random.default_rng(seed).choice(n, rows, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name, t in outputs.items():
+        assert t.shape[0] == n, f"{name}: first axis {t.shape[0]} is not the env axis ({n})"
+        sel = t if rows == n else t.index_select(0, torch.from_numpy(idx).to(t.device))
+        a = sel.detach().cpu().numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+        paths.append(os.path.join(out_dir, f"{name}.npy"))
+        np.save(paths[-1], a)
+    paths.append(os.path.join(out_dir, "env_index.npy"))
+    np.save(paths[-1], (env_index_base + idx).astype(np.float64))
+    return paths
 
 
 def host_cores() -> int:
@@ -212,7 +240,7 @@ def main():
     use_events = not args.no_profile_events
     markers = os.environ.get("TE_PROF") == "markers"
 
-    def measure(n_local: int, headline_only: bool, scaling: str) -> dict:
+    def measure(n_local: int, headline_only: bool, scaling: str, dump_dir=None) -> dict:
         """Everything measured on one shard size: the headline window, and (unless headline_only) the steady-state and all-armed regimes.
         Returns the JSON line's fields (meaningful on rank 0)."""
         cfg = default_config(args.task, n_envs=n_local, env_index_base=rank * n_local, **overrides)
@@ -241,17 +269,29 @@ def main():
                 for i in range(n_total):
                     env.random_actions(args.action_seed + 1000, i, out=ally_actions[i])
 
+        step_names = ("stacked", "mask", "inertial", "last_action", "reward", "done", "info") if cfg.stacked_obs else \
+            ("lidar", "inertial", "last_action", "reward", "done", "info")
+        last = [None]   # (ally observation, step outputs) the latest step handed its caller: views of the env's buffers
+
         def one_step(i: int):
+            ally = None
             if external:
-                env.observe_ally()
+                ally = env.observe_ally()
                 if not pregen:
                     env.random_actions(args.action_seed + 1000, i, out=ally_actions[0])
                 env.set_ally_actions(ally_actions[i if pregen else 0])
             if pregen:
-                step_fn(actions[i], terminal=True)
+                res = step_fn(actions[i], terminal=True)
             else:
                 env.random_actions(args.action_seed, i, out=actions[0])
-                step_fn(actions[0], terminal=True)
+                res = step_fn(actions[0], terminal=True)
+            last[0] = (ally, res)
+
+        def dump_last_step():
+            ally, res = last[0]
+            named = dict(zip(("ally_lidar", "ally_inertial", "ally_last_action", "ally_active"), ally)) if ally is not None else {}
+            named.update(zip(step_names, res))
+            dump_outputs(dump_dir, named, env_index_base=rank * n_local)
 
         def armed_per_env() -> float:
             """Mean number of armed drones per env (disarmed slots are not flown: they cost one flag load)."""
@@ -304,7 +344,7 @@ def main():
                     + ("marker packets between the launches (TE_PROF=markers: each bracket includes ~5 us of queue time)" if markers else
                        "the kernels' own start / stop events (hipExtLaunchKernel: dispatch begin / end timestamps, as in rocprofv3 --kernel-trace)"))
 
-        def regime(first: int, count: int, n_events: int, label: str):
+        def regime(first: int, count: int, n_events: int, label: str, after_timed=None):
             """One measured regime of the rollout: `count` steps on the wall clock (no events), then — unless n_events is 0 — the same
             `count` steps once more from the saved state with the kernels timed by HIP events.  Every fraction of the HBM peak is
             computed from the WALL time of the step."""
@@ -312,6 +352,8 @@ def main():
             replay = use_events and n_events > 0
             saved = env.get_state().clone() if replay else None
             el = timed(first, count)
+            if after_timed is not None:   # before the event replay overwrites the outputs (with the same values)
+                after_timed()
             a1 = armed_per_env() if rank == 0 else 0.0
             k1_ms = k2_ms = 0.0; n_prof = 0
             if replay:   # the SAME steps again from the saved state (the rollout is deterministic), this time with the kernels timed
@@ -337,7 +379,9 @@ def main():
             one_step(i)
         torch.cuda.synchronize(device)
         # ---- headline: EXACTLY args.steps steps after args.warmup, nothing else in the timed region
-        head, elapsed, (k1_ms, k2_ms, n_prof, armed) = regime(args.warmup, args.steps, args.steps, "headline")
+        head, elapsed, (k1_ms, k2_ms, n_prof, armed) = regime(
+            args.warmup, args.steps, args.steps, "headline",
+            after_timed=dump_last_step if dump_dir else None)
         done_frac = float(env.done.float().mean().item())
         extra = {}
         if not headline_only:
@@ -446,15 +490,16 @@ def main():
     # te_step enqueues on the caller's stream (BatchedEnv passes torch's current one): the legacy null stream unless --own-stream.
     # Interleaved A/B on one box (round 3): 851 / 851 / 861 M env-steps/s on the null stream against 848 / 855 / 846 M on a
     # stream of the bench's own in the driver's window — no difference.
+    dump_dir = args.dump_outputs if rank == 0 else None   # rank 0's shard of the headline window
     import contextlib
     lane = torch.cuda.stream(torch.cuda.Stream(device)) if args.own_stream else contextlib.nullcontext()
     with lane:
         if args.envs_per_gpu:       # an explicit shard size: per-GPU work fixed as N grows
-            out = measure(args.envs_per_gpu, args.headline_only, "weak")
+            out = measure(args.envs_per_gpu, args.headline_only, "weak", dump_dir)
         else:                       # BASELINE.json's configuration: --total-envs in total, split over the ranks
             if args.total_envs % world:
                 raise SystemExit(f"--total-envs {args.total_envs} does not split over {world} ranks")
-            out = measure(args.total_envs // world, args.headline_only, "strong")   # the metric's configuration: total fixed, at every N incl. 1
+            out = measure(args.total_envs // world, args.headline_only, "strong", dump_dir)   # the metric's configuration: total fixed, at every N incl. 1
             if world > 1 and not args.no_weak_block:
                 # the size one MI355X is efficient at, on every rank: what the node delivers when the caller has 65 536 envs PER GPU
                 wk = measure(args.total_envs, True, "weak")
