@@ -16,7 +16,8 @@
 //                            and the flight plan of the next step -> patch the hit cells into the background.
 // (te_step_stacked adds stacked_kernel, te_stacked.hpp; exp05 brackets te_step with te_observe_ally /
 // te_set_ally_actions.)
-// No MFMA: this is element-wise physics and byte streaming.
+// No MFMA: this is element-wise physics and byte streaming.  The one MFMA kernel of the library is the policy's
+// inference, te_policy_act (te_policy.hpp), which is not part of te_step.
 //
 // Reference citations are file:line under the reference's src/ tree.
 #include <hip/hip_runtime.h>
@@ -37,6 +38,7 @@
 #include "te_stackview.hpp"
 #include "te_engage.hpp"
 #include "te_engage_slots.hpp"
+#include "te_policy.hpp"
 
 namespace te {
 
@@ -1801,4 +1803,50 @@ __attribute__((visibility("default"))) int te_debug_stamps(te_env* e, uint64_t* 
   return 0;
 }
 
+static int policy_words(int32_t lidar_channels, size_t* out) {
+  if (lidar_channels != 2 && lidar_channels != 3) return fail("te_policy: lidar_channels must be 2 or 3");
+  *out = (size_t)policy_layout(lidar_channels).words;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_param_words(int32_t lidar_channels, size_t* out_words) {
+  if (!out_words) return fail("te_policy_param_words: null argument");
+  return policy_words(lidar_channels, out_words);
+}
+
+__attribute__((visibility("default"))) int te_policy_act(const float* params, int32_t lidar_channels, int32_t n, const float* lidar,
+                                                         const float* inertial, const float* last_action, const float* eps, float* mu,
+                                                         float* value, float* action, float* logp, float* action_env, void* stream) {
+  size_t words;
+  if (policy_words(lidar_channels, &words)) return 1;
+  if (n <= 0) return fail("te_policy_act: n must be positive");
+  if (!params || !lidar || !inertial || !last_action || !mu || !value) return fail("te_policy_act: null argument");
+  if (eps && (!action || !logp || !action_env)) return fail("te_policy_act: eps given, so action, logp and action_env must be too");
+  if ((uintptr_t)params & 15) return fail("te_policy_act: params must be 16-byte aligned");
+  if ((uintptr_t)lidar & 7) return fail("te_policy_act: lidar must be 8-byte aligned");
+  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)eps, (const void*)mu, (const void*)value,
+                        (const void*)action, (const void*)logp, (const void*)action_env})
+    if ((uintptr_t)q & 3) return fail("te_policy_act: float arrays must be 4-byte aligned");
+  const void* fn = lidar_channels == 3 ? reinterpret_cast<const void*>(&policy_act_kernel<3>) : reinterpret_cast<const void*>(&policy_act_kernel<2>);
+  // kPolLdsBytes is above the 64 KB a launch gets by default: opt in once per (device, kernel); not a stream operation, so a
+  // capturing stream allows it
+  static uint64_t opted[2] = {0, 0};
+  int dev = 0;
+  TE_HIP(hipGetDevice(&dev));
+  uint64_t& bits = opted[lidar_channels - 2];
+  if (dev < 64 && !(bits >> dev & 1)) {
+    TE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes));
+    bits |= 1ull << dev;
+  }
+  PolicyParams P = policy_layout(lidar_channels);
+  P.base = params;
+  const PolicyIO io{lidar, inertial, last_action, eps, mu, value, eps ? action : nullptr, eps ? logp : nullptr, eps ? action_env : nullptr, n};
+  const dim3 grid((unsigned)((n + kPolTileM - 1) / kPolTileM));
+  if (lidar_channels == 3) hipLaunchKernelGGL(policy_act_kernel<3>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, io);
+  else hipLaunchKernelGGL(policy_act_kernel<2>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, io);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // extern "C"
+

@@ -1,0 +1,254 @@
+// te_policy.hpp — inference of LidarInertialActionPolicy (dronechase_amd/ppo.py) in one launch: the forward pass, the
+// Gaussian sample and its log-probability, and the action clamp te_step takes (te_policy_act, include/threatengage.h).
+//
+//   policy_act_kernel  one 256-thread workgroup (4 waves) per tile of kTileM = 32 rows.  Every layer is a GEMM on
+//                      v_mfma_f32_16x16x4_f32 (f32 in, f32 accumulate): the tile's activations stay in LDS from layer to
+//                      layer, the weights are read straight from the packed parameter buffer (0.94 MB: L2-resident and
+//                      shared by every workgroup of the XCD).  A wave owns one 16-column slice of a layer's output at a
+//                      time, for both 16-row halves of the tile: one 16-byte weight load feeds 8 MFMAs.  Barriers separate
+//                      the layers.
+//
+// Layer by layer (C = LIDAR channels, 2 or 3):
+//   conv1 (k4 s4) as a GEMM over non-overlapping 4x4 patches, [32 rows x 4 positions, 16 C] x [16 C, 32], computed
+//     for one conv2 output column at a time (3 chunks): conv2 (k2 s2) reads rows 0-1 of conv1's 3 x 6 output only, so
+//     conv1 needs 12 of its 18 positions and the LIDAR rows 8-12 and columns 24-25 are never read.  A lane reads a
+//     patch row of 4 cells as two 8-byte loads (a LIDAR row is 104 bytes: 8-byte, not 16-byte aligned).  The output
+//     lands in LDS already in conv2's patch order (ci * 4 + kh * 2 + kw).
+//   conv2 as [32, 128] x [128, 64] per chunk, scattered into the flatten order (co * 3 + column) of the feature row.
+//   inertial_data [15] and last_action [4], zero-padded to K = 16, through 3 x Linear(128) + ReLU each.
+//   concat [448] -> Linear(256) + ReLU -> pi: 2 x Linear(64) + tanh, vf: 2 x Linear(64) + tanh.
+//   mu = Linear(64, 4) and value = Linear(64, 1) on the vector ALU, one thread per row.
+//
+// Numerics: fp32 throughout.  A k-block of 16 is consumed as 4 MFMAs whose k index is strided by 4 (lane group h holds
+// k0 + 4h .. k0 + 4h + 3 as one float4; MFMA s takes component s), so the sum order differs from PyTorch's; the
+// accumulator starts from the bias.  The order is fixed per output element and does not depend on where the row sits in
+// the tile, on the tile, or on N: a row's outputs are bitwise the same in any call.
+#pragma once
+
+namespace te {
+
+constexpr int kPolTileM = 32;           // rows per workgroup (two 16-row MFMA tiles)
+constexpr int kPolThreads = 256;        // 4 waves
+constexpr int kPolZS = 448 + 4;         // LDS row strides in floats (+4: a 16-lane float4 column read spreads over the banks)
+constexpr int kPolTS = 128 + 4;
+constexpr int kPolFS = 256 + 4;
+constexpr int kPolPS = 64 + 4;
+constexpr int kPolZWords = kPolTileM * kPolZS;                     // concat features; later the heads' activations
+constexpr int kPolUWords = 2 * kPolTileM * kPolTS;                 // two 128-wide ping-pong tiles; later the 256-wide trunk
+static_assert(kPolTileM * kPolFS <= kPolUWords, "trunk tile fits the ping-pong region");
+static_assert(2 * kPolTileM * kPolPS + kPolTileM * 4 <= kPolZWords, "head tiles fit the feature region");
+constexpr int kPolLdsBytes = (kPolZWords + kPolUWords) * 4;
+
+// Float offsets of every tensor in the packed parameter buffer (the public layout of threatengage.h).
+struct PolicyParams {
+  const float* base;
+  int c1w, c1b, c2w, c2b;
+  int in_w[3], in_b[3], ac_w[3], ac_b[3];
+  int fw, fb, pi_w[2], pi_b[2], vf_w[2], vf_b[2], muw, mub, vw, vb, log_std;
+  int words;
+};
+
+inline PolicyParams policy_layout(int C) {
+  PolicyParams p{};
+  int o = 0;
+  auto take = [&](int n) { int at = o; o += n; return at; };
+  p.c1w = take(32 * 16 * C); p.c1b = take(32);
+  p.c2w = take(64 * 128);    p.c2b = take(64);
+  for (int i = 0; i < 3; ++i) { p.in_w[i] = take(128 * (i ? 128 : 15)); p.in_b[i] = take(128); }
+  for (int i = 0; i < 3; ++i) { p.ac_w[i] = take(128 * (i ? 128 : 4)); p.ac_b[i] = take(128); }
+  p.fw = take(256 * 448); p.fb = take(256);
+  for (int i = 0; i < 2; ++i) { p.pi_w[i] = take(64 * (i ? 64 : 256)); p.pi_b[i] = take(64); }
+  for (int i = 0; i < 2; ++i) { p.vf_w[i] = take(64 * (i ? 64 : 256)); p.vf_b[i] = take(64); }
+  p.muw = take(4 * 64); p.mub = take(4);
+  p.vw = take(64); p.vb = take(1);
+  p.log_std = take(4);
+  p.words = o;
+  return p;
+}
+
+struct PolicyIO {
+  const float *lidar, *inertial, *last_action, *eps;
+  float *mu, *value, *action, *logp, *action_env;
+  int n;
+};
+
+typedef float pol_f32x4 __attribute__((ext_vector_type(4)));
+
+enum { POL_RELU = 0, POL_TANH = 1 };
+
+TE_DEV pol_f32x4 pol_mfma4(float4 a, float4 b, pol_f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+  return acc;
+}
+
+// Y[32, N] = act(X[32, K] W^T + b) with X in LDS (row stride ldx, columns K .. roundup(K, 16) zero), W [N][K] row-major in
+// global memory.  store(row, col, value) writes one output element.  Lane l of a 16 x 16 tile: A = X[l & 15][k0 + 4 (l >> 4) + s],
+// B = W[n0 + (l & 15)][k0 + 4 (l >> 4) + s]; C/D: column l & 15, rows 4 (l >> 4) .. +3.
+template <int K, int N, int ACT, class Store>
+TE_DEV void pol_dense(const float* X, int ldx, const float* __restrict__ W, const float* __restrict__ bias, Store store) {
+  static_assert(N % 16 == 0 && N / 16 >= kPolThreads / 64, "every wave owns at least one 16-column slice");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, h = lane >> 4;
+  for (int nt = wave; nt < N / 16; nt += kPolThreads / 64) {
+    const int n = nt * 16 + r;
+    const float b0 = bias[n];
+    pol_f32x4 acc0 = {b0, b0, b0, b0}, acc1 = acc0;
+    const float* wr = W + (size_t)n * K;
+#pragma unroll 4
+    for (int k0 = 0; k0 < K; k0 += 16) {
+      const int k = k0 + 4 * h;
+      float4 w;
+      if constexpr (K % 4 == 0) {
+        w = k < K ? *reinterpret_cast<const float4*>(wr + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {  // K = 15: rows are not 16-byte aligned
+        w.x = k + 0 < K ? wr[k + 0] : 0.f; w.y = k + 1 < K ? wr[k + 1] : 0.f;
+        w.z = k + 2 < K ? wr[k + 2] : 0.f; w.w = k + 3 < K ? wr[k + 3] : 0.f;
+      }
+      const float4 a0 = *reinterpret_cast<const float4*>(X + r * ldx + k);
+      const float4 a1 = *reinterpret_cast<const float4*>(X + (16 + r) * ldx + k);
+      acc0 = pol_mfma4(a0, w, acc0);
+      acc1 = pol_mfma4(a1, w, acc1);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float v0 = acc0[i], v1 = acc1[i];
+      if constexpr (ACT == POL_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
+      else { v0 = tanhf(v0); v1 = tanhf(v1); }
+      store(4 * h + i, n, v0);
+      store(16 + 4 * h + i, n, v1);
+    }
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(kPolThreads) void policy_act_kernel(PolicyParams P, PolicyIO io) {
+  extern __shared__ __attribute__((aligned(16))) float pol_lds[];
+  float* Z = pol_lds;                          // [32][kPolZS]: lidar 0..191 | inertial 192..319 | last_action 320..447
+  float* T1 = pol_lds + kPolZWords;            // [32][kPolTS]
+  float* T2 = T1 + kPolTileM * kPolTS;         // [32][kPolTS]
+  float* F = T1;                               // [32][kPolFS] once T1 / T2 are dead
+  float* P1 = Z;                               // [32][kPolPS] once Z is dead
+  float* P2 = Z + kPolTileM * kPolPS;
+  float* MU = Z + 2 * kPolTileM * kPolPS;      // [32][4]
+  const float* __restrict__ prm = P.base;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, h = lane >> 4;
+  const int row0 = blockIdx.x * kPolTileM;
+  auto to = [](float* Y, int ld) { return [=](int m, int n, float v) { Y[m * ld + n] = v; }; };
+
+  // ---- LIDAR: conv1 + conv2, one conv2 output column (ow2) at a time
+  {
+    // wave w computes conv1 position (oh, j) = (w >> 1, w & 1) of the chunk for both row halves and all 32 channels
+    const int oh = wave >> 1, j = wave & 1;
+    for (int ow2 = 0; ow2 < 3; ++ow2) {
+      const int ow = 2 * ow2 + j;
+      pol_f32x4 acc[2][2];
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const float b = prm[P.c1b + nt * 16 + r];
+        acc[0][nt] = pol_f32x4{b, b, b, b}; acc[1][nt] = acc[0][nt];
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c) {      // k-block c: k = c * 16 + kh * 4 + kw, lane group h = kh
+        float4 a[2], w[2];
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+          const int row = row0 + half * 16 + r;
+          a[half] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (row < io.n) {
+            const float* src = io.lidar + ((size_t)row * C + c) * (13 * 26) + (4 * oh + h) * 26 + 4 * ow;
+            const float2 lo = *reinterpret_cast<const float2*>(src), hi = *reinterpret_cast<const float2*>(src + 2);
+            a[half] = make_float4(lo.x, lo.y, hi.x, hi.y);
+          }
+        }
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) w[nt] = *reinterpret_cast<const float4*>(prm + P.c1w + (nt * 16 + r) * (16 * C) + c * 16 + 4 * h);
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+#pragma unroll
+          for (int nt = 0; nt < 2; ++nt) acc[half][nt] = pol_mfma4(a[half], w[nt], acc[half][nt]);
+      }
+      // conv1 output (row, co, oh, ow) -> conv2 patch of column ow2: T1[row][co * 4 + oh * 2 + j]
+#pragma unroll
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            T1[(half * 16 + 4 * h + i) * kPolTS + (nt * 16 + r) * 4 + oh * 2 + j] = fmaxf(acc[half][nt][i], 0.f);
+      __syncthreads();
+      pol_dense<128, 64, POL_RELU>(T1, kPolTS, prm + P.c2w, prm + P.c2b,
+                                   [=](int m, int n, float v) { Z[m * kPolZS + n * 3 + ow2] = v; });
+      __syncthreads();
+    }
+  }
+
+  // ---- inertial_data and last_action: 3 x (Linear(128) + ReLU) each, into Z columns 192 and 320
+  for (int t = tid; t < kPolTileM * 16; t += kPolThreads) {
+    const int m = t >> 4, k = t & 15, row = row0 + m;
+    T1[m * kPolTS + k] = (row < io.n && k < 15) ? io.inertial[(size_t)row * 15 + k] : 0.f;
+    T2[m * kPolTS + k] = (row < io.n && k < 4) ? io.last_action[(size_t)row * 4 + k] : 0.f;
+  }
+  __syncthreads();
+  // each chain ping-pongs between its own 128 columns of Z and T1 (T2 holds last_action's input until its first layer)
+  pol_dense<15, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[0], prm + P.in_b[0], [=](int m, int n, float v) { Z[m * kPolZS + 192 + n] = v; });
+  __syncthreads();
+  pol_dense<128, 128, POL_RELU>(Z + 192, kPolZS, prm + P.in_w[1], prm + P.in_b[1], to(T1, kPolTS));
+  __syncthreads();
+  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[2], prm + P.in_b[2], [=](int m, int n, float v) { Z[m * kPolZS + 192 + n] = v; });
+  __syncthreads();
+  pol_dense<4, 128, POL_RELU>(T2, kPolTS, prm + P.ac_w[0], prm + P.ac_b[0], [=](int m, int n, float v) { Z[m * kPolZS + 320 + n] = v; });
+  __syncthreads();
+  pol_dense<128, 128, POL_RELU>(Z + 320, kPolZS, prm + P.ac_w[1], prm + P.ac_b[1], to(T1, kPolTS));
+  __syncthreads();
+  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.ac_w[2], prm + P.ac_b[2], [=](int m, int n, float v) { Z[m * kPolZS + 320 + n] = v; });
+  __syncthreads();
+
+  // ---- trunk: concat [448] -> Linear(256) + ReLU
+  pol_dense<448, 256, POL_RELU>(Z, kPolZS, prm + P.fw, prm + P.fb, to(F, kPolFS));
+  __syncthreads();
+
+  const float* log_std = prm + P.log_std;
+  // ---- pi head, then mu (one thread per row)
+  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.pi_w[0], prm + P.pi_b[0], to(P1, kPolPS));
+  __syncthreads();
+  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.pi_w[1], prm + P.pi_b[1], to(P2, kPolPS));
+  __syncthreads();
+  if (tid < kPolTileM) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      float s = prm[P.mub + a];
+      for (int k = 0; k < 64; ++k) s = fmaf(P2[tid * kPolPS + k], prm[P.muw + a * 64 + k], s);
+      MU[tid * 4 + a] = s;
+    }
+  }
+  __syncthreads();
+  // ---- vf head, then value and the outputs of the row (the thread that computed mu reads it back: no barrier needed)
+  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.vf_w[0], prm + P.vf_b[0], to(P1, kPolPS));
+  __syncthreads();
+  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.vf_w[1], prm + P.vf_b[1], to(P2, kPolPS));
+  __syncthreads();
+  const int row = row0 + tid;
+  if (tid < kPolTileM && row < io.n) {
+    float v = prm[P.vb];
+    for (int k = 0; k < 64; ++k) v = fmaf(P2[tid * kPolPS + k], prm[P.vw + k], v);
+    io.value[row] = v;
+    float lp = 0.f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const float mu = MU[tid * 4 + a];
+      io.mu[(size_t)row * 4 + a] = mu;
+      if (io.eps) {
+        const float e = io.eps[(size_t)row * 4 + a], ls = log_std[a];
+        const float act = fmaf(expf(ls), e, mu);
+        lp += -0.5f * e * e - ls - 0.9189385332046727f;
+        if (io.action) io.action[(size_t)row * 4 + a] = act;
+        if (io.action_env) io.action_env[(size_t)row * 4 + a] = fmaxf(fminf(act, 1.f), a < 3 ? -1.f : 0.f);
+      }
+    }
+    if (io.eps && io.logp) io.logp[row] = lp;
+  }
+}
+
+}  // namespace te

@@ -13,6 +13,8 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
     state-independent log-std (stable_baselines3 ActorCriticPolicy defaults);
   * losses / GAE = the PPO of Schulman et al. 2017 with SB3's defaults (clip 0.2, gae_lambda 0.95, gamma 0.99,
     vf_coef 0.5, ent_coef 0, max_grad_norm 0.5, advantage normalisation per minibatch, 10 epochs);
+  * PPOConfig.fused_forward: the rollout's forward, sampling and log-prob in one HIP launch (te_policy_act, FusedPolicy below)
+    instead of ~40 PyTorch launches per step; update() keeps autograd through the module;
   * multi-GPU: one process per GPU, each with its own env shard; gradients are averaged with
     torch.distributed all_reduce (RCCL) — the only collective of the whole system, once per minibatch.
 """
@@ -21,8 +23,12 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Dict, Optional
 
+import ctypes as C
+
 import torch
 import torch.nn as nn
+
+from . import _lib
 
 
 class LidarInertialActionPolicy(nn.Module):
@@ -61,20 +67,108 @@ class LidarInertialActionPolicy(nn.Module):
         return torch.distributions.Normal(mu, self.log_std.exp().expand_as(mu), validate_args=False), v
 
 
-class PolicyDriver:
-    """SB3-style `predict` over a LidarInertialActionPolicy, on the device: what ThreatEngageVecEnv.update_model (exp05:
-    the ally flown by a copy of the learning policy, apps/threatengage_runner/stage03/experiments/05/
-    bo_exp05_vFinal_home_office_app.py:140,179) takes when the observations should not leave HBM."""
-    accepts_torch = True
+def _packed_order(policy: nn.Module):
+    """The public layout of te_policy_act's parameter buffer (include/threatengage.h): the submodules' parameters in registration
+    order, then log_std.  (parameters() itself yields log_std first: a module's own parameters precede its children's.)"""
+    named = list(policy.named_parameters())
+    return [p for n, p in named if n != "log_std"] + [policy.log_std]
+
+
+@torch.no_grad()
+def pack_policy(policy: nn.Module, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The policy's weights in te_policy_act's layout; into `out` in place (same storage) when given."""
+    flat = [p.detach().reshape(-1).float() for p in _packed_order(policy)]
+    return torch.cat(flat) if out is None else torch.cat(flat, out=out)
+
+
+def policy_param_words(lidar_channels: int) -> int:
+    out = C.c_size_t()
+    _lib.check(_lib.load().te_policy_param_words(int(lidar_channels), C.byref(out)), "te_policy_param_words")
+    return int(out.value)
+
+
+class FusedPolicy:
+    """Inference of a LidarInertialActionPolicy by te_policy_act: the forward pass, the Gaussian sample, its log-prob and the
+    clamp of the action in one HIP launch.  The weights are packed into ONE device buffer that keeps its address for the life of
+    this object; refresh() repacks the module's current weights into it in place, so a HIP graph that captured a call sees them.
+    Call refresh() after every change of the module's weights (PPO does, at the start of every collect())."""
 
     def __init__(self, policy: nn.Module):
         self.policy = policy
+        self.lidar_channels = int(policy.lidar[0].in_channels)
+        params = _packed_order(policy)
+        self.device = params[0].device
+        if self.device.type != "cuda":
+            raise ValueError("FusedPolicy runs the HIP kernel te_policy_act: the policy must live on a GPU")
+        words = policy_param_words(self.lidar_channels)
+        if sum(p.numel() for p in params) != words:
+            raise ValueError(f"policy has {sum(p.numel() for p in params)} parameters, te_policy_act's layout {words}: not a LidarInertialActionPolicy")
+        self.params = torch.empty(words, dtype=torch.float32, device=self.device)
+        self.refresh()
+
+    def refresh(self) -> None:
+        pack_policy(self.policy, out=self.params)
+
+    def _call(self, obs, eps, outs):
+        lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
+        n = lidar.shape[0]
+        for name, t, shape in (("lidar", lidar, (n, self.lidar_channels, 13, 26)), ("inertial_data", inertial, (n, 15)),
+                               ("last_action", last_action, (n, 4)), ("eps", eps, (n, 4))):
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"FusedPolicy: {name} must be a contiguous float32 {shape} tensor on {self.device}")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(_lib.load().te_policy_act(self.params.data_ptr(), self.lidar_channels, n, lidar.data_ptr(), inertial.data_ptr(),
+                                                 last_action.data_ptr(), ptr(eps), *(ptr(o) for o in outs), stream), "te_policy_act")
+
+    def forward(self, obs: Dict[str, torch.Tensor]):
+        """(mu [N, 4], value [N]) of the module's forward."""
+        n = obs["lidar"].shape[0]
+        mu = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        value = torch.empty((n,), dtype=torch.float32, device=self.device)
+        self._call(obs, None, (mu, value, None, None, None))
+        return mu, value
+
+    __call__ = forward
+
+    def act(self, obs: Dict[str, torch.Tensor], eps: torch.Tensor):
+        """(a, logp, value, a_env) for the standard-normal draw eps [N, 4]: a = mu + exp(log_std) eps, logp its log-density summed
+        over the 4 components, a_env = a clamped to [-1, 1]^3 x [0, 1]."""
+        n = obs["lidar"].shape[0]
+        f = dict(dtype=torch.float32, device=self.device)
+        mu, value, a, logp, a_env = torch.empty((n, 4), **f), torch.empty((n,), **f), torch.empty((n, 4), **f), torch.empty((n,), **f), torch.empty((n, 4), **f)
+        self._call(obs, eps, (mu, value, a, logp, a_env))
+        return a, logp, value, a_env
+
+
+class PolicyDriver:
+    """SB3-style `predict` over a LidarInertialActionPolicy, on the device: what ThreatEngageVecEnv.update_model (exp05:
+    the ally flown by a copy of the learning policy, apps/threatengage_runner/stage03/experiments/05/
+    bo_exp05_vFinal_home_office_app.py:140,179) takes when the observations should not leave HBM.
+    fused=True: the forward (and the sample) is one te_policy_act launch (FusedPolicy); the weights are repacked at every call,
+    so a policy trained in between is always the one that flies."""
+    accepts_torch = True
+
+    def __init__(self, policy: nn.Module, fused: bool = False):
+        self.policy = policy
+        self.fused = FusedPolicy(policy) if fused else None
         self.low = None
 
     @torch.no_grad()
     def predict(self, observation: Dict[str, torch.Tensor], state=None, episode_start=None, deterministic: bool = True):
-        dist, _ = self.policy.dist(observation)
-        a = dist.mean if deterministic else dist.sample()
+        if self.fused is not None:
+            self.fused.refresh()
+            obs = {k: observation[k].contiguous() for k in ("lidar", "inertial_data", "last_action")}
+            if deterministic:
+                a = self.fused.forward(obs)[0]
+            else:
+                return self.fused.act(obs, torch.randn((obs["lidar"].shape[0], 4), device=self.fused.device))[3], None
+        else:
+            dist, _ = self.policy.dist(observation)
+            a = dist.mean if deterministic else dist.sample()
         if self.low is None:
             self.low = torch.tensor([-1.0, -1.0, -1.0, 0.0], device=a.device)
         return torch.max(torch.min(a, torch.ones_like(a)), self.low), None
@@ -97,6 +191,10 @@ class PPOConfig:
     # backward of the policy (fp32 master weights, fp32 losses and optimiser): measured + 16 % on the update at 32 768-sample minibatches
     # (tools/ppo_update_profile.py).  Off by default: fp32 / plain Adam is what SB3 runs.
     fast_learner: bool = False
+    # collect() and the bootstrap value: the policy's forward + sampling + log-prob + clamp as ONE HIP launch (te_policy_act, FusedPolicy)
+    # instead of the op-by-op PyTorch forward; eps still comes from torch.randn_like, update() still runs the PyTorch module.
+    # Off by default: the outputs agree with the module's to ~1.5e-7 (measured), not bit for bit (another summation order)
+    fused_forward: bool = False
     reward_scale: float = 1e-3   # rewards reach +-1000 (exp03_vFinal_task.py:423-515); SB3 users wrap VecNormalize
 
 
@@ -167,6 +265,9 @@ class PPO:
             p.grad = self._flat_grad[off:off + p.numel()].view_as(p)
             off += p.numel()
         env.reset()
+        if self.cfg.fused_forward and self.device.type != "cuda":
+            raise ValueError("PPOConfig.fused_forward runs the HIP kernel te_policy_act: it needs a GPU device")
+        self.fused = FusedPolicy(self.policy) if self.cfg.fused_forward else None
         self.direct = env.N % 2 == 0   # slot t of the LIDAR buffer starts on a 16-byte boundary (4 056 bytes per env)
         self._obs = None               # set by the first collect(): te_observe of the reset state
         self.num_timesteps = 0
@@ -191,13 +292,18 @@ class PPO:
         def step_once():
             # the diagonal Gaussian by hand: torch.normal on expanded tensors checks its arguments on the host, which
             # a capturing stream does not permit.  log N(a; mu, sigma) = -(a - mu)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi)
-            mu, v = self.policy(self._g_obs)
-            log_std = self.policy.log_std
-            eps = torch.randn_like(mu)
-            a = mu + log_std.exp() * eps
-            logp = (-0.5 * eps * eps - log_std - 0.9189385332046727).sum(-1)
+            if self.fused is not None:     # the same draw (randn_like of an [N, 4] float32 tensor), then one launch
+                eps = torch.randn_like(self._g["a"])
+                a, logp, v, a_env = self.fused.act(self._g_obs, eps)
+            else:
+                mu, v = self.policy(self._g_obs)
+                log_std = self.policy.log_std
+                eps = torch.randn_like(mu)
+                a = mu + log_std.exp() * eps
+                logp = (-0.5 * eps * eps - log_std - 0.9189385332046727).sum(-1)
+                a_env = torch.max(torch.min(a, self.high), self.low).contiguous()
             self._g["a"].copy_(a); self._g["logp"].copy_(logp); self._g["v"].copy_(v)
-            lidar, inertial, last_action, reward, done, _ = self.env.step(torch.max(torch.min(a, self.high), self.low).contiguous(), terminal=False)
+            lidar, inertial, last_action, reward, done, _ = self.env.step(a_env, terminal=False)
             self._g["reward"].copy_(reward); self._g["done"].copy_(done)
             self._g_obs["lidar"].copy_(lidar); self._g_obs["inertial_data"].copy_(inertial); self._g_obs["last_action"].copy_(last_action)
 
@@ -231,13 +337,15 @@ class PPO:
             torch.mul(self._g["reward"], c.reward_scale, out=b.rewards[t]); b.dones[t].copy_(self._g["done"])
             ep_rew += self._g["reward"].mean(); ep_n += self._g["done"].sum().long()
         self._obs = self._g_obs
-        _, last_v = self.policy(self._obs)
+        _, last_v = (self.fused or self.policy)(self._obs)
         b.finish(last_v, c.gamma, c.gae_lambda)
         self.num_timesteps += c.n_steps * self.env.N
         return {"mean_step_reward": float(ep_rew) / c.n_steps, "episodes_finished": int(ep_n)}
 
     @torch.no_grad()
     def collect(self) -> Dict[str, float]:
+        if self.fused is not None:   # update() moved the module's weights: repack them into the buffer the captured graph reads
+            self.fused.refresh()
         if self.cfg.use_graph and self.device.type == "cuda":
             return self._collect_graph()
         return self._collect_eager()
@@ -254,12 +362,16 @@ class PPO:
         for k in b.obs:
             b.obs[k][0].copy_(self._obs[k])
         for t in range(c.n_steps):
-            dist, v = self.policy.dist({k: o[t] for k, o in b.obs.items()})
-            a = dist.sample()
-            b.actions[t], b.logp[t], b.values[t] = a, dist.log_prob(a).sum(-1), v
+            if self.fused is not None:
+                a, logp, v, a_env = self.fused.act({k: o[t] for k, o in b.obs.items()}, torch.randn_like(b.actions[t]))
+                b.actions[t], b.logp[t], b.values[t] = a, logp, v
+            else:
+                dist, v = self.policy.dist({k: o[t] for k, o in b.obs.items()})
+                a = dist.sample()
+                b.actions[t], b.logp[t], b.values[t] = a, dist.log_prob(a).sum(-1), v
+                a_env = torch.max(torch.min(a, self.high), self.low).contiguous()
             dest = self._slot(t + 1) if (self.direct and t + 1 < c.n_steps) else None
-            lidar, inertial, last_action, reward, done, _info = self.env.step(torch.max(torch.min(a, self.high), self.low).contiguous(),
-                                                                              terminal=False, out=dest)
+            lidar, inertial, last_action, reward, done, _info = self.env.step(a_env, terminal=False, out=dest)
             if dest is None and t + 1 < c.n_steps:   # odd n_envs: the slots are not 16-byte aligned, copy instead
                 for k, src in zip(("lidar", "inertial_data", "last_action"), (lidar, inertial, last_action)):
                     b.obs[k][t + 1].copy_(src)
@@ -267,7 +379,7 @@ class PPO:
             b.dones[t] = done.float()
             ep_rew += reward.mean(); ep_n += done.sum()   # stays on the device: one sync per rollout, not per step
         self._obs = {"lidar": lidar, "inertial_data": inertial, "last_action": last_action}
-        _, last_v = self.policy(self._obs)
+        _, last_v = (self.fused or self.policy)(self._obs)
         ep_rew, ep_n = float(ep_rew), int(ep_n)
         b.finish(last_v, c.gamma, c.gae_lambda)
         self.num_timesteps += c.n_steps * self.env.N

@@ -420,6 +420,29 @@ int te_profile_end(te_env* env, float* substeps_ms, float* engage_observe_ms, in
  * zeros otherwise.  out_host is HOST memory. */
 int te_debug_stamps(te_env* env, uint64_t* out_host, int32_t n);
 
+/* Inference of the PPO policy (dronechase_amd/ppo.py LidarInertialActionPolicy; the reference's SB3 MultiInputPolicy with
+ * LidarInertialActionExtractor, src/core/rl_framework/agents/policies/ppo_policies.py:234-341) in one launch, fp32.
+ *
+ * `params` is ONE packed device buffer of te_policy_param_words(lidar_channels) floats, 16-byte aligned: the module's parameters
+ * in the registration order of its submodules, each flattened row-major as PyTorch stores it, then log_std:
+ *   lidar.0.weight [32][C][4][4], lidar.0.bias [32], lidar.2.weight [64][32][2][2], lidar.2.bias [64],
+ *   inertial.{0,2,4}.{weight,bias} ([128][15], [128], [128][128], [128], [128][128], [128]),
+ *   action.{0,2,4}.{weight,bias} ([128][4], [128], then as inertial), final.0.weight [256][448], final.0.bias [256],
+ *   pi.{0,2}.{weight,bias} ([64][256], [64], [64][64], [64]), vf.{0,2}.{weight,bias} (as pi),
+ *   mu.weight [4][64], mu.bias [4], value.weight [1][64], value.bias [1], log_std [4].
+ * C = lidar_channels (3, or 2 for the legacy LIDAR layout): 235 049 words for C = 3, 512 fewer for C = 2.
+ *
+ * te_policy_act: n rows of lidar [n][C][13][26] (8-byte aligned), inertial [n][15], last_action [n][4] -> mu [n][4], value [n].
+ * With eps [n][4] (a standard-normal draw) it also samples: action = mu + exp(log_std) * eps (unclamped, what PPO stores),
+ * logp [n] = sum_j (-eps_j^2 / 2 - log_std_j - log(2 pi) / 2), action_env = action clamped to [-1, 1]^3 x [0, 1] (what te_step
+ * takes).  action, logp and action_env may be NULL when eps is NULL.  Rows are independent: a row's outputs do not depend on n
+ * or on the other rows.  Enqueues on `stream` only (no allocation, no host synchronisation: a HIP graph can capture it); runs on
+ * the current device. */
+int te_policy_param_words(int32_t lidar_channels, size_t* out_words);
+int te_policy_act(const float* params, int32_t lidar_channels, int32_t n, const float* lidar, const float* inertial,
+                  const float* last_action, const float* eps, float* mu, float* value, float* action, float* logp,
+                  float* action_env, void* stream);
+
 int te_abi_version(void);
 const char* te_last_error(void);
 
