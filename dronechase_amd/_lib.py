@@ -17,7 +17,7 @@ EXPORTS = (
     "te_config_default", "te_create", "te_destroy", "te_reset", "te_observe", "te_step", "te_random_actions",
     "te_state_words", "te_get_state", "te_set_state", "te_algorithmic_bytes_per_env_step", "te_profile_begin",
     "te_profile_end", "te_debug_stamps", "te_abi_version", "te_last_error", "te_step_stacked", "te_observe_stacked", "te_observe_ally", "te_set_ally_actions", "te_wingman_info", "te_calculate_rounds", "te_observe_wingman", "te_set_wingman_actions", "te_quad_preset", "te_step_students", "te_set_persistent_obs",
-    "te_policy_param_words", "te_policy_act",
+    "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad",
 )
 
 
@@ -69,6 +69,9 @@ def load() -> C.CDLL:
     L.te_profile_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)]
     L.te_policy_param_words.argtypes = [i32, C.POINTER(C.c_size_t)]
     L.te_policy_act.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
+    L.te_policy_grad_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
+    f32 = C.c_float
+    L.te_policy_ppo_grad.argtypes = [vp, i32, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]
     if L.te_abi_version() != K.TE_ABI_VERSION:
         raise RuntimeError("libthreatengage.so ABI version differs from dronechase_amd.config")
     _LIB = L

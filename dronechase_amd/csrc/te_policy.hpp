@@ -72,6 +72,13 @@ struct PolicyIO {
   int n;
 };
 
+// The rows a forward reads: row i of the tile set is read at index[i] (NULL: at i) of lidar / inertial / last_action.
+struct PolicyIn {
+  const float *lidar, *inertial, *last_action;
+  const int64_t* index;
+  int n;
+};
+
 typedef float pol_f32x4 __attribute__((ext_vector_type(4)));
 
 enum { POL_RELU = 0, POL_TANH = 1 };
@@ -84,28 +91,22 @@ TE_DEV pol_f32x4 pol_mfma4(float4 a, float4 b, pol_f32x4 acc) {
   return acc;
 }
 
-// Y[32, N] = act(X[32, K] W^T + b) with X in LDS (row stride ldx, columns K .. roundup(K, 16) zero), W [N][K] row-major in
-// global memory.  store(row, col, value) writes one output element.  Lane l of a 16 x 16 tile: A = X[l & 15][k0 + 4 (l >> 4) + s],
-// B = W[n0 + (l & 15)][k0 + 4 (l >> 4) + s]; C/D: column l & 15, rows 4 (l >> 4) .. +3.
-template <int K, int N, int ACT, class Store>
-TE_DEV void pol_dense(const float* X, int ldx, const float* __restrict__ W, const float* __restrict__ bias, Store store) {
+// Y[32, N] = X[32, K] B + init, the GEMM every layer of the policy runs (forward and backward).  X in LDS (row stride ldx,
+// columns K .. roundup(K, 16) zero); loadb(n, k) returns B[k .. k + 3][n] (k a multiple of 4, zero past K); init(n) starts the
+// accumulator of column n; epi(row, col, value) consumes one output element.  Lane l of a 16 x 16 tile:
+// A = X[l & 15][k0 + 4 (l >> 4) + s], B = B[k0 + 4 (l >> 4) + s][n0 + (l & 15)]; C/D: column l & 15, rows 4 (l >> 4) .. +3.
+template <int K, int N, class LoadB, class Init, class Epi>
+TE_DEV void pol_gemm(const float* X, int ldx, LoadB loadb, Init init, Epi epi) {
   static_assert(N % 16 == 0 && N / 16 >= kPolThreads / 64, "every wave owns at least one 16-column slice");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, h = lane >> 4;
   for (int nt = wave; nt < N / 16; nt += kPolThreads / 64) {
     const int n = nt * 16 + r;
-    const float b0 = bias[n];
+    const float b0 = init(n);
     pol_f32x4 acc0 = {b0, b0, b0, b0}, acc1 = acc0;
-    const float* wr = W + (size_t)n * K;
 #pragma unroll 4
     for (int k0 = 0; k0 < K; k0 += 16) {
       const int k = k0 + 4 * h;
-      float4 w;
-      if constexpr (K % 4 == 0) {
-        w = k < K ? *reinterpret_cast<const float4*>(wr + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-      } else {  // K = 15: rows are not 16-byte aligned
-        w.x = k + 0 < K ? wr[k + 0] : 0.f; w.y = k + 1 < K ? wr[k + 1] : 0.f;
-        w.z = k + 2 < K ? wr[k + 2] : 0.f; w.w = k + 3 < K ? wr[k + 3] : 0.f;
-      }
+      const float4 w = loadb(n, k);
       const float4 a0 = *reinterpret_cast<const float4*>(X + r * ldx + k);
       const float4 a1 = *reinterpret_cast<const float4*>(X + (16 + r) * ldx + k);
       acc0 = pol_mfma4(a0, w, acc0);
@@ -113,29 +114,71 @@ TE_DEV void pol_dense(const float* X, int ldx, const float* __restrict__ W, cons
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      float v0 = acc0[i], v1 = acc1[i];
-      if constexpr (ACT == POL_RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-      else { v0 = tanhf(v0); v1 = tanhf(v1); }
-      store(4 * h + i, n, v0);
-      store(16 + 4 * h + i, n, v1);
+      epi(4 * h + i, n, acc0[i]);
+      epi(16 + 4 * h + i, n, acc1[i]);
     }
   }
 }
 
-template <int C>
-__global__ __launch_bounds__(kPolThreads) void policy_act_kernel(PolicyParams P, PolicyIO io) {
-  extern __shared__ __attribute__((aligned(16))) float pol_lds[];
+// Y[32, N] = act(X[32, K] W^T + b), W [N][K] row-major in global memory (the forward of a Linear layer): pol_gemm with
+// B[k][n] = W[n][k], the accumulator starting from the bias.  store(row, col, value) writes one output element.
+template <int K, int N, int ACT, class Store>
+TE_DEV void pol_dense(const float* X, int ldx, const float* __restrict__ W, const float* __restrict__ bias, Store store) {
+  pol_gemm<K, N>(
+      X, ldx,
+      [=](int n, int k) {
+        const float* wr = W + (size_t)n * K;
+        float4 w;
+        if constexpr (K % 4 == 0) {
+          w = k < K ? *reinterpret_cast<const float4*>(wr + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {  // K = 15: rows are not 16-byte aligned
+          w.x = k + 0 < K ? wr[k + 0] : 0.f; w.y = k + 1 < K ? wr[k + 1] : 0.f;
+          w.z = k + 2 < K ? wr[k + 2] : 0.f; w.w = k + 3 < K ? wr[k + 3] : 0.f;
+        }
+        return w;
+      },
+      [=](int n) { return bias[n]; },
+      [=](int m, int n, float v) { store(m, n, ACT == POL_RELU ? fmaxf(v, 0.f) : tanhf(v)); });
+}
+
+// What pol_forward hands to its `save` hook besides keeping it in LDS: every layer's input, i.e. what the weight gradient of that
+// layer needs.  save(buf, m, sub, col, v): tile row m, sub-row sub (a conv position), column col.
+enum {
+  POL_SV_C1X = 0,   // conv1 patches: sub = conv1 position p = ow2 * 4 + oh * 2 + j (0..11), col = c * 16 + kh * 4 + kw
+  POL_SV_C2X,       // conv2 patches (conv1 output after ReLU): sub = ow2 (0..2), col = ci * 4 + kh * 2 + kw
+  POL_SV_IN0X, POL_SV_IN1X, POL_SV_IN2X,   // inputs of inertial.{0,2,4}: [15], [128], [128]
+  POL_SV_AC0X, POL_SV_AC1X, POL_SV_AC2X,   // inputs of action.{0,2,4}: [4], [128], [128]
+  POL_SV_FX,        // the concat [448] (conv2 output in flatten order co * 3 + ow2, inertial, last_action): input of final.0
+  POL_SV_F,         // the trunk [256]: input of pi.0 and vf.0
+  POL_SV_PI1X, POL_SV_MUX, POL_SV_VF1X, POL_SV_VX,   // [64] each: inputs of pi.2, mu, vf.2, value
+  POL_SV_COUNT
+};
+
+struct PolNoSave {
+  TE_DEV void operator()(int, int, int, int, float) const {}
+};
+
+// LDS of pol_forward once it returns: MU [32][4] and VAL [32] (rows of the tile), written by thread tid = row for tid < 32.
+TE_DEV float* pol_mu_lds(float* lds) { return lds + 2 * kPolTileM * kPolPS; }
+TE_DEV float* pol_val_lds(float* lds) { return lds + 2 * kPolTileM * kPolPS + kPolTileM * 4; }
+static_assert(2 * kPolTileM * kPolPS + kPolTileM * 5 <= kPolZWords, "MU and VAL fit the feature region");
+
+// The forward of the 32 rows from row0 (rows >= in.n read zeros): mu and value of every row into pol_mu_lds / pol_val_lds; each
+// layer's input also goes to save().  Thread tid < 32 computes row tid's mu and value and may read them back without a barrier.
+template <int C, class Save>
+TE_DEV void pol_forward(const PolicyParams& P, const PolicyIn& in, float* pol_lds, int row0, Save save) {
   float* Z = pol_lds;                          // [32][kPolZS]: lidar 0..191 | inertial 192..319 | last_action 320..447
   float* T1 = pol_lds + kPolZWords;            // [32][kPolTS]
   float* T2 = T1 + kPolTileM * kPolTS;         // [32][kPolTS]
   float* F = T1;                               // [32][kPolFS] once T1 / T2 are dead
   float* P1 = Z;                               // [32][kPolPS] once Z is dead
   float* P2 = Z + kPolTileM * kPolPS;
-  float* MU = Z + 2 * kPolTileM * kPolPS;      // [32][4]
+  float* MU = pol_mu_lds(pol_lds);             // [32][4]
+  float* VAL = pol_val_lds(pol_lds);           // [32]
   const float* __restrict__ prm = P.base;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, h = lane >> 4;
-  const int row0 = blockIdx.x * kPolTileM;
-  auto to = [](float* Y, int ld) { return [=](int m, int n, float v) { Y[m * ld + n] = v; }; };
+  auto src = [&](int row) -> size_t { return in.index ? (size_t)in.index[row] : (size_t)row; };
+  auto to = [=](float* Y, int ld, int sv) { return [=](int m, int n, float v) { Y[m * ld + n] = v; save(sv, m, 0, n, v); }; };
 
   // ---- LIDAR: conv1 + conv2, one conv2 output column (ow2) at a time
   {
@@ -156,11 +199,14 @@ __global__ __launch_bounds__(kPolThreads) void policy_act_kernel(PolicyParams P,
         for (int half = 0; half < 2; ++half) {
           const int row = row0 + half * 16 + r;
           a[half] = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (row < io.n) {
-            const float* src = io.lidar + ((size_t)row * C + c) * (13 * 26) + (4 * oh + h) * 26 + 4 * ow;
-            const float2 lo = *reinterpret_cast<const float2*>(src), hi = *reinterpret_cast<const float2*>(src + 2);
+          if (row < in.n) {
+            const float* s = in.lidar + (src(row) * C + c) * (13 * 26) + (4 * oh + h) * 26 + 4 * ow;
+            const float2 lo = *reinterpret_cast<const float2*>(s), hi = *reinterpret_cast<const float2*>(s + 2);
             a[half] = make_float4(lo.x, lo.y, hi.x, hi.y);
           }
+          const int m = half * 16 + r, p = ow2 * 4 + oh * 2 + j, col = c * 16 + 4 * h;
+          save(POL_SV_C1X, m, p, col + 0, a[half].x); save(POL_SV_C1X, m, p, col + 1, a[half].y);
+          save(POL_SV_C1X, m, p, col + 2, a[half].z); save(POL_SV_C1X, m, p, col + 3, a[half].w);
         }
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) w[nt] = *reinterpret_cast<const float4*>(prm + P.c1w + (nt * 16 + r) * (16 * C) + c * 16 + 4 * h);
@@ -175,11 +221,15 @@ __global__ __launch_bounds__(kPolThreads) void policy_act_kernel(PolicyParams P,
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
-            T1[(half * 16 + 4 * h + i) * kPolTS + (nt * 16 + r) * 4 + oh * 2 + j] = fmaxf(acc[half][nt][i], 0.f);
+          for (int i = 0; i < 4; ++i) {
+            const int m = half * 16 + 4 * h + i, col = (nt * 16 + r) * 4 + oh * 2 + j;
+            const float v = fmaxf(acc[half][nt][i], 0.f);
+            T1[m * kPolTS + col] = v;
+            save(POL_SV_C2X, m, ow2, col, v);
+          }
       __syncthreads();
       pol_dense<128, 64, POL_RELU>(T1, kPolTS, prm + P.c2w, prm + P.c2b,
-                                   [=](int m, int n, float v) { Z[m * kPolZS + n * 3 + ow2] = v; });
+                                   [=](int m, int n, float v) { Z[m * kPolZS + n * 3 + ow2] = v; save(POL_SV_FX, m, 0, n * 3 + ow2, v); });
       __syncthreads();
     }
   }
@@ -187,33 +237,39 @@ __global__ __launch_bounds__(kPolThreads) void policy_act_kernel(PolicyParams P,
   // ---- inertial_data and last_action: 3 x (Linear(128) + ReLU) each, into Z columns 192 and 320
   for (int t = tid; t < kPolTileM * 16; t += kPolThreads) {
     const int m = t >> 4, k = t & 15, row = row0 + m;
-    T1[m * kPolTS + k] = (row < io.n && k < 15) ? io.inertial[(size_t)row * 15 + k] : 0.f;
-    T2[m * kPolTS + k] = (row < io.n && k < 4) ? io.last_action[(size_t)row * 4 + k] : 0.f;
+    const float vi = (row < in.n && k < 15) ? in.inertial[src(row) * 15 + k] : 0.f;
+    const float va = (row < in.n && k < 4) ? in.last_action[src(row) * 4 + k] : 0.f;
+    T1[m * kPolTS + k] = vi;
+    T2[m * kPolTS + k] = va;
+    if (k < 15) save(POL_SV_IN0X, m, 0, k, vi);
+    if (k < 4) save(POL_SV_AC0X, m, 0, k, va);
   }
   __syncthreads();
   // each chain ping-pongs between its own 128 columns of Z and T1 (T2 holds last_action's input until its first layer)
-  pol_dense<15, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[0], prm + P.in_b[0], [=](int m, int n, float v) { Z[m * kPolZS + 192 + n] = v; });
+  auto toZ = [=](int col0, int sv) {
+    return [=](int m, int n, float v) { Z[m * kPolZS + col0 + n] = v; save(sv, m, 0, sv == POL_SV_FX ? col0 + n : n, v); };
+  };
+  pol_dense<15, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[0], prm + P.in_b[0], toZ(192, POL_SV_IN1X));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(Z + 192, kPolZS, prm + P.in_w[1], prm + P.in_b[1], to(T1, kPolTS));
+  pol_dense<128, 128, POL_RELU>(Z + 192, kPolZS, prm + P.in_w[1], prm + P.in_b[1], to(T1, kPolTS, POL_SV_IN2X));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[2], prm + P.in_b[2], [=](int m, int n, float v) { Z[m * kPolZS + 192 + n] = v; });
+  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[2], prm + P.in_b[2], toZ(192, POL_SV_FX));
   __syncthreads();
-  pol_dense<4, 128, POL_RELU>(T2, kPolTS, prm + P.ac_w[0], prm + P.ac_b[0], [=](int m, int n, float v) { Z[m * kPolZS + 320 + n] = v; });
+  pol_dense<4, 128, POL_RELU>(T2, kPolTS, prm + P.ac_w[0], prm + P.ac_b[0], toZ(320, POL_SV_AC1X));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(Z + 320, kPolZS, prm + P.ac_w[1], prm + P.ac_b[1], to(T1, kPolTS));
+  pol_dense<128, 128, POL_RELU>(Z + 320, kPolZS, prm + P.ac_w[1], prm + P.ac_b[1], to(T1, kPolTS, POL_SV_AC2X));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.ac_w[2], prm + P.ac_b[2], [=](int m, int n, float v) { Z[m * kPolZS + 320 + n] = v; });
+  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.ac_w[2], prm + P.ac_b[2], toZ(320, POL_SV_FX));
   __syncthreads();
 
   // ---- trunk: concat [448] -> Linear(256) + ReLU
-  pol_dense<448, 256, POL_RELU>(Z, kPolZS, prm + P.fw, prm + P.fb, to(F, kPolFS));
+  pol_dense<448, 256, POL_RELU>(Z, kPolZS, prm + P.fw, prm + P.fb, to(F, kPolFS, POL_SV_F));
   __syncthreads();
 
-  const float* log_std = prm + P.log_std;
   // ---- pi head, then mu (one thread per row)
-  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.pi_w[0], prm + P.pi_b[0], to(P1, kPolPS));
+  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.pi_w[0], prm + P.pi_b[0], to(P1, kPolPS, POL_SV_PI1X));
   __syncthreads();
-  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.pi_w[1], prm + P.pi_b[1], to(P2, kPolPS));
+  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.pi_w[1], prm + P.pi_b[1], to(P2, kPolPS, POL_SV_MUX));
   __syncthreads();
   if (tid < kPolTileM) {
 #pragma unroll
@@ -224,16 +280,29 @@ __global__ __launch_bounds__(kPolThreads) void policy_act_kernel(PolicyParams P,
     }
   }
   __syncthreads();
-  // ---- vf head, then value and the outputs of the row (the thread that computed mu reads it back: no barrier needed)
-  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.vf_w[0], prm + P.vf_b[0], to(P1, kPolPS));
+  // ---- vf head, then value (the thread that computed mu computes the value: no barrier needed)
+  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.vf_w[0], prm + P.vf_b[0], to(P1, kPolPS, POL_SV_VF1X));
   __syncthreads();
-  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.vf_w[1], prm + P.vf_b[1], to(P2, kPolPS));
+  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.vf_w[1], prm + P.vf_b[1], to(P2, kPolPS, POL_SV_VX));
   __syncthreads();
-  const int row = row0 + tid;
-  if (tid < kPolTileM && row < io.n) {
+  if (tid < kPolTileM) {
     float v = prm[P.vb];
     for (int k = 0; k < 64; ++k) v = fmaf(P2[tid * kPolPS + k], prm[P.vw + k], v);
-    io.value[row] = v;
+    VAL[tid] = v;
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(kPolThreads) void policy_act_kernel(PolicyParams P, PolicyIO io) {
+  extern __shared__ __attribute__((aligned(16))) float pol_lds[];
+  const PolicyIn in{io.lidar, io.inertial, io.last_action, nullptr, io.n};
+  const int tid = threadIdx.x, row = blockIdx.x * kPolTileM + tid;
+  pol_forward<C>(P, in, pol_lds, blockIdx.x * kPolTileM, PolNoSave{});
+  // the outputs of the row, read back by the thread that computed them
+  const float* MU = pol_mu_lds(pol_lds);
+  const float* log_std = P.base + P.log_std;
+  if (tid < kPolTileM && row < io.n) {
+    io.value[row] = pol_val_lds(pol_lds)[tid];
     float lp = 0.f;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {

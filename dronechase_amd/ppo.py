@@ -14,7 +14,9 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
   * losses / GAE = the PPO of Schulman et al. 2017 with SB3's defaults (clip 0.2, gae_lambda 0.95, gamma 0.99,
     vf_coef 0.5, ent_coef 0, max_grad_norm 0.5, advantage normalisation per minibatch, 10 epochs);
   * PPOConfig.fused_forward: the rollout's forward, sampling and log-prob in one HIP launch (te_policy_act, FusedPolicy below)
-    instead of ~40 PyTorch launches per step; update() keeps autograd through the module;
+    instead of ~40 PyTorch launches per step;
+  * PPOConfig.fused_update: the minibatch's loss gradient in one ABI call (te_policy_ppo_grad, FusedPolicy.ppo_grad) instead of
+    the PyTorch forward + autograd, reading the rollout rows through the minibatch index (no gather of the observations);
   * multi-GPU: one process per GPU, each with its own env shard; gradients are averaged with
     torch.distributed all_reduce (RCCL) — the only collective of the whole system, once per minibatch.
 """
@@ -109,6 +111,50 @@ class FusedPolicy:
     def refresh(self) -> None:
         pack_policy(self.policy, out=self.params)
 
+    def ppo_grad(self, obs: Dict[str, torch.Tensor], index: Optional[torch.Tensor], action: torch.Tensor, old_logp: torch.Tensor,
+                 adv: torch.Tensor, ret: torch.Tensor, adv_mean_std: Optional[torch.Tensor], clip: float, vf_coef: float,
+                 ent_coef: float, grad_out: torch.Tensor, stats_out: torch.Tensor) -> None:
+        """The gradient of PPO's loss over the minibatch rows `index` (int64 [B]; None: every row) of the rollout tensors obs,
+        action [M, 4], old_logp, adv and ret [M], in the packed layout, into grad_out [te_policy_param_words] (16-byte aligned);
+        stats_out [4] = pg, vl, ent, clip_frac.  adv_mean_std [2] (mean, unbiased std of adv over the minibatch) normalises the
+        advantage; None uses it as it is.  One te_policy_ppo_grad call: three launches, no host synchronisation.  The
+        workspace (~17.5 KB per row) is owned here and grows on demand, which a capturing stream does not allow: make the first
+        call of a size outside capture."""
+        lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
+        m = lidar.shape[0]
+        b = m if index is None else index.shape[0]
+        checks = [("lidar", lidar, (m, self.lidar_channels, 13, 26)), ("inertial_data", inertial, (m, 15)), ("last_action", last_action, (m, 4)),
+                  ("action", action, (m, 4)), ("old_logp", old_logp, (m,)), ("adv", adv, (m,)), ("ret", ret, (m,)),
+                  ("adv_mean_std", adv_mean_std, (2,)), ("grad_out", grad_out, (self.params.numel(),)), ("stats_out", stats_out, (4,))]
+        for name, t, shape in checks:
+            if t is None:
+                if name == "adv_mean_std":
+                    continue
+                raise ValueError(f"FusedPolicy.ppo_grad: {name} is required")
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"FusedPolicy.ppo_grad: {name} must be a contiguous float32 {shape} tensor on {self.device}")
+        if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != self.device or not index.is_contiguous()):
+            raise ValueError(f"FusedPolicy.ppo_grad: index must be a contiguous 1-D int64 tensor on {self.device}")
+        if b == 0:
+            raise ValueError("FusedPolicy.ppo_grad: the minibatch is empty")
+        lib = _lib.load()
+        need = C.c_size_t()
+        _lib.check(lib.te_policy_grad_workspace_bytes(self.lidar_channels, b, C.byref(need)), "te_policy_grad_workspace_bytes")
+        ws = getattr(self, "_grad_ws", None)
+        if ws is None or ws.numel() < need.value:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedPolicy.ppo_grad: the workspace must grow, which a capturing stream does not allow; "
+                                   "call once with this minibatch size before capture")
+            self._grad_ws = None           # free the old workspace before the larger one is allocated
+            ws = self._grad_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(lib.te_policy_ppo_grad(self.params.data_ptr(), self.lidar_channels, b, ptr(index), lidar.data_ptr(), inertial.data_ptr(),
+                                              last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                                              ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef), grad_out.data_ptr(),
+                                              stats_out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "te_policy_ppo_grad")
+
     def _call(self, obs, eps, outs):
         lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
         n = lidar.shape[0]
@@ -195,6 +241,11 @@ class PPOConfig:
     # instead of the op-by-op PyTorch forward; eps still comes from torch.randn_like, update() still runs the PyTorch module.
     # Off by default: the outputs agree with the module's to ~1.5e-7 (measured), not bit for bit (another summation order)
     fused_forward: bool = False
+    # update(): the minibatch's loss gradient in ONE ABI call (te_policy_ppo_grad, FusedPolicy.ppo_grad: forward, loss, backward and
+    # deterministic split-K weight gradients in HIP, the rows read through the minibatch index) instead of the PyTorch forward +
+    # autograd; gradient clipping, the all-reduce and Adam stay as they are (with fast_learner: fused Adam, no autocast).
+    # Off by default: the gradient agrees with autograd's to a tolerance (another summation order), not bit for bit
+    fused_update: bool = False
     reward_scale: float = 1e-3   # rewards reach +-1000 (exp03_vFinal_task.py:423-515); SB3 users wrap VecNormalize
 
 
@@ -258,7 +309,8 @@ class PPO:
         # ONE gradient bucket: every parameter's .grad is a view of this flat buffer, so data-parallel training averages the
         # gradients of a minibatch with a single all-reduce (RCCL over xGMI: a ring is per-link bound, 25 small collectives per
         # minibatch would be latency-bound; the policy has ~0.3 M parameters = 1.2 MB, one bucket)
-        params = [p for p in self.policy.parameters() if p.requires_grad]
+        # fused_update: the bucket in te_policy_act's packed order, so te_policy_ppo_grad writes the .grad views directly
+        params = _packed_order(self.policy) if self.cfg.fused_update else [p for p in self.policy.parameters() if p.requires_grad]
         self._flat_grad = torch.zeros(sum(p.numel() for p in params), dtype=params[0].dtype, device=self.device)
         off = 0
         for p in params:
@@ -267,7 +319,11 @@ class PPO:
         env.reset()
         if self.cfg.fused_forward and self.device.type != "cuda":
             raise ValueError("PPOConfig.fused_forward runs the HIP kernel te_policy_act: it needs a GPU device")
+        if self.cfg.fused_update and self.device.type != "cuda":
+            raise ValueError("PPOConfig.fused_update runs the HIP kernels of te_policy_ppo_grad: it needs a GPU device")
         self.fused = FusedPolicy(self.policy) if self.cfg.fused_forward else None
+        self.fused_grad = (self.fused or FusedPolicy(self.policy)) if self.cfg.fused_update else None
+        self._grad_stats = torch.zeros(4, device=self.device)
         self.direct = env.N % 2 == 0   # slot t of the LIDAR buffer starts on a 16-byte boundary (4 056 bytes per env)
         self._obs = None               # set by the first collect(): te_observe of the reset state
         self.num_timesteps = 0
@@ -394,11 +450,16 @@ class PPO:
         # running sums stay on the device: one host read per update(), not four per minibatch (each float() drains the stream)
         acc = torch.zeros(4, device=self.device)
         n_batches = 0
-        amp = bool(c.fast_learner) and self.device.type == "cuda"
+        amp = bool(c.fast_learner) and self.device.type == "cuda" and not c.fused_update
         for _ in range(c.n_epochs):
             perm = torch.randperm(T * N, device=self.device)
             for s in range(0, T * N, c.batch_size):
                 idx = perm[s:s + c.batch_size]
+                if self.fused_grad is not None:
+                    self._fused_minibatch(obs, idx, actions, old_logp, adv, ret)
+                    acc += self._grad_stats
+                    n_batches += 1
+                    continue
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
                     mu, v = self.policy({k: o[idx] for k, o in obs.items()})
                 mu, v = mu.float(), v.float()
@@ -423,6 +484,21 @@ class PPO:
                 n_batches += 1
         pg_s, vl_s, ent_s, clip_s = (acc / max(n_batches, 1)).tolist()
         return {"pg_loss": pg_s, "v_loss": vl_s, "entropy": ent_s, "clip_frac": clip_s}
+
+    def _fused_minibatch(self, obs, idx, actions, old_logp, adv, ret) -> None:
+        """One minibatch of update() with fused_update: the gradient of the loss straight into the flat gradient bucket by
+        te_policy_ppo_grad, then the same all-reduce, clipping and Adam step as the autograd path."""
+        c = self.cfg
+        self.fused_grad.refresh()            # Adam moved the weights: repack them (one 0.94 MB device copy)
+        a = adv[idx]
+        ms = torch.stack((a.mean(), a.std()))
+        self.fused_grad.ppo_grad(obs, idx, actions, old_logp, adv, ret, ms, c.clip_range, c.vf_coef, c.ent_coef,
+                                 self._flat_grad, self._grad_stats)
+        if self.distributed:
+            torch.distributed.all_reduce(self._flat_grad)
+            self._flat_grad.div_(torch.distributed.get_world_size())
+        nn.utils.clip_grad_norm_(self.policy.parameters(), c.max_grad_norm)
+        self.opt.step()
 
     def learn(self, total_timesteps: int, log=None):
         while self.num_timesteps < total_timesteps:

@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""The PPO learner's minibatch: autograd fp32 (plain Adam), PPOConfig.fast_learner (bf16 autocast + fused Adam) and
+PPOConfig.fused_update (te_policy_ppo_grad, te_policy_grad.hpp) at 8 192, 16 384 and 65 536 rows, each one update() of one
+minibatch (gradient + clip + Adam) on a collected stage03 rollout; the te_policy_ppo_grad call alone against its fp32 MFMA bound;
+then tools/ppo_split.py's 65 536-env collect + update with fused_forward=True, fused_update=True.  One JSON document on stdout.
+    python tools/policy_update_bench.py [n_envs_for_split] [n_steps] [epochs]
+Bound: forward + activation gradients (all but conv1's, inertial.0's and action.0's inputs) + weight gradients, 2 FLOP per MAC, at
+the 157.3 TF fp32 MFMA peak."""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from dronechase_amd import default_config
+from dronechase_amd.batched_env import BatchedEnv
+from dronechase_amd.ppo import PPO, PPOConfig
+
+N_SPLIT = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
+T = int(sys.argv[2]) if len(sys.argv) > 2 else 32
+E = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+FWD = 32 * 48 * 12 + 64 * 128 * 3 + (15 * 128 + 2 * 128 * 128) + (4 * 128 + 2 * 128 * 128) + 448 * 256 + 2 * (256 * 64 + 64 * 64) + 64 * 5
+MACS_PER_ROW = 3 * FWD - (32 * 48 * 12 + 15 * 128 + 4 * 128)
+PEAK_TFLOPS = 157.3
+
+
+def timed(fn, reps):
+    torch.cuda.synchronize(); t = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / reps
+
+
+out = {"macs_per_row": MACS_PER_ROW, "minibatch": []}
+for rows in (8192, 16384, 65536):
+    rec = {"rows": rows, "bound_ms": 2.0 * MACS_PER_ROW * rows / (PEAK_TFLOPS * 1e12) * 1e3}
+    for key, kw in (("autograd_fp32_ms", {}), ("fast_learner_ms", {"fast_learner": True}), ("fused_update_ms", {"fused_update": True})):
+        env = BatchedEnv(default_config("stage03", n_envs=rows), "cuda:0")
+        ppo = PPO(env, PPOConfig(n_steps=1, batch_size=rows, n_epochs=1, use_graph=False, **kw), seed=3)
+        ppo.collect()
+        for _ in range(3):
+            ppo.update()                     # warm-up: MIOpen algorithm search, the fused path's workspace
+        rec[key] = timed(ppo.update, 20) * 1e3
+        if "fused_update" in kw:            # the gradient call alone, on the same rows
+            b = ppo.buf
+            obs = {k: v.reshape(rows, *v.shape[2:]) for k, v in b.obs.items()}
+            idx = torch.randperm(rows, device="cuda:0")
+            ms = torch.tensor([0.0, 1.0], device="cuda:0")
+            st = torch.empty(4, device="cuda:0")
+            call = lambda: ppo.fused_grad.ppo_grad(obs, idx, b.actions.reshape(rows, 4), b.logp.reshape(-1), b.adv.reshape(-1),
+                                                   b.ret.reshape(-1), ms, 0.2, 0.5, 0.0, ppo._flat_grad, st)
+            call()
+            t = timed(call, 50)
+            rec["te_policy_ppo_grad_ms"] = t * 1e3
+            rec["te_policy_ppo_grad_TFLOPS"] = 2.0 * MACS_PER_ROW * rows / t / 1e12
+            rec["fraction_of_fp32_mfma_peak"] = rec["te_policy_ppo_grad_TFLOPS"] / PEAK_TFLOPS
+        env.close(); del ppo
+        torch.cuda.empty_cache()
+    rec["speedup_vs_autograd_fp32"] = rec["autograd_fp32_ms"] / rec["fused_update_ms"]
+    rec["speedup_vs_fast_learner"] = rec["fast_learner_ms"] / rec["fused_update_ms"]
+    out["minibatch"].append(rec)
+
+# tools/ppo_split.py's measurement with both fused paths on
+env = BatchedEnv(default_config("stage03", n_envs=N_SPLIT), "cuda:0")
+ppo = PPO(env, PPOConfig(n_steps=T, batch_size=N_SPLIT, n_epochs=E, use_graph=True, fused_forward=True, fused_update=True), seed=3)
+ppo.collect(); ppo.update()                  # graph capture, workspace
+t_col = timed(ppo.collect, 3)
+t_upd = timed(ppo.update, 2)
+stats = ppo.update()
+mbs = E * ((T * N_SPLIT + N_SPLIT - 1) // N_SPLIT)
+out["split"] = {"n_envs": N_SPLIT, "n_steps": T, "batch_size": N_SPLIT, "n_epochs": E, "fused_forward": True, "fused_update": True,
+                "collect_s": t_col, "collect_us_per_step": t_col / T * 1e6, "collect_Msteps_per_s": T * N_SPLIT / t_col / 1e6,
+                "update_s": t_upd, "update_ms_per_minibatch": t_upd / mbs * 1e3, "update_Msamples_per_s": E * T * N_SPLIT / t_upd / 1e6,
+                "collect_plus_update_Msteps_per_s": T * N_SPLIT / (t_col + t_upd) / 1e6,
+                "finite": all(v == v and abs(v) < 1e30 for v in stats.values()), "last_update": stats}
+env.close()
+print(json.dumps(out, indent=1))
