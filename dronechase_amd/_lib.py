@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libthreaten
 EXPORTS = (
     "te_config_default", "te_create", "te_destroy", "te_reset", "te_observe", "te_step", "te_random_actions",
     "te_state_words", "te_get_state", "te_set_state", "te_algorithmic_bytes_per_env_step", "te_profile_begin",
-    "te_profile_end", "te_debug_stamps", "te_abi_version", "te_last_error", "te_step_stacked", "te_observe_stacked", "te_observe_ally", "te_set_ally_actions", "te_wingman_info", "te_calculate_rounds", "te_observe_wingman", "te_set_wingman_actions", "te_quad_preset", "te_step_students", "te_set_persistent_obs",
+    "te_profile_end", "te_debug_stamps", "te_abi_version", "te_last_error", "te_step_stacked", "te_observe_stacked", "te_observe_ally", "te_set_ally_actions", "te_wingman_info", "te_calculate_rounds", "te_observe_wingman", "te_set_wingman_actions", "te_drive_wingman", "te_quad_preset", "te_step_students", "te_set_persistent_obs",
     "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad",
 )
 
@@ -58,6 +58,7 @@ def load() -> C.CDLL:
     L.te_calculate_rounds.argtypes = [C.c_int32, C.c_int32]
     L.te_observe_wingman.argtypes = [vp, C.c_int32] + [vp] * 4 + [vp]
     L.te_set_wingman_actions.argtypes = [vp, C.c_int32, vp, vp]
+    L.te_drive_wingman.argtypes = [vp, i32, vp, i32] + [vp] * 4 + [vp]
     L.te_random_actions.argtypes = [vp, vp, u64, u64, vp]
     L.te_state_words.argtypes = [vp, C.POINTER(C.c_size_t)]
     L.te_get_state.argtypes = [vp, vp, C.c_size_t, vp]

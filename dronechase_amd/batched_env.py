@@ -169,6 +169,28 @@ class BatchedEnv:
         a = self._check_actions(actions)
         _lib.check(self.L.te_set_wingman_actions(self._h, int(wingman), self._p(a), self._stream()), "te_set_wingman_actions")
 
+    def wingman_scratch(self, wingman: int):
+        """The observation buffers drive_wingman fills for pursuer `wingman` (lidar, inertial, last_action; overwritten by every
+        call).  Allocated on first use: call once before a HIP graph captures drive_wingman."""
+        if not hasattr(self, "_drive_buf"):
+            self._drive_buf = {}
+        if wingman not in self._drive_buf:
+            self._drive_buf[wingman] = (torch.empty_like(self.lidar), torch.empty_like(self.inertial), torch.empty_like(self.last_action))
+        return self._drive_buf[wingman]
+
+    def drive_wingman(self, wingman: int, fused_policy, mu: Optional[torch.Tensor] = None) -> None:
+        """drive_lw_rl_agent for a caller-driven pursuer in one te_drive_wingman call: its observation, the deterministic action of
+        `fused_policy` (a ppo.FusedPolicy: its packed buffer is read at launch time) and the drive of every env whose pursuer is
+        armed.  mu [N, 4] f32 (optional) receives the unclamped mean of every row.  No allocation after the first call and no host
+        synchronisation: a HIP graph can capture it."""
+        lidar, inertial, last_action = self.wingman_scratch(wingman)
+        if fused_policy.device != self.device:
+            raise ValueError(f"drive_wingman: the policy lives on {fused_policy.device}, the env on {self.device}")
+        if mu is not None and (tuple(mu.shape) != (self.N, 4) or mu.dtype != torch.float32 or mu.device != self.device or not mu.is_contiguous()):
+            raise ValueError(f"drive_wingman: mu must be a contiguous float32 [{self.N}, 4] tensor on {self.device}")
+        _lib.check(self.L.te_drive_wingman(self._h, int(wingman), self._p(fused_policy.params), int(fused_policy.lidar_channels), self._p(lidar),
+                                           self._p(inertial), self._p(last_action), self._p(mu), self._stream()), "te_drive_wingman")
+
     def observe_ally(self):
         """exp05: the ally = pursuer 1 (Exp05_vFinal_Task.compute_lw_observation)."""
         if int(self.cfg.ally_policy) != K.ALLY_EXTERNAL:

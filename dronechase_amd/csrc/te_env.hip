@@ -15,9 +15,10 @@
 //                            spawn phase, one (env, slot) per thread -> observation rows + the allies' commands
 //                            and the flight plan of the next step -> patch the hit cells into the background.
 // (te_step_stacked adds stacked_kernel, te_stacked.hpp; exp05 brackets te_step with te_observe_ally /
-// te_set_ally_actions.)
+// te_set_ally_actions, or with te_drive_wingman when a packed policy flies the ally.)
 // No MFMA: this is element-wise physics and byte streaming.  The MFMA kernels of the library are the policy's
-// inference, te_policy_act (te_policy.hpp), and its PPO gradient, te_policy_ppo_grad (te_policy_grad.hpp); neither is part of te_step.
+// inference, te_policy_act (te_policy.hpp) and te_drive_wingman's policy_drive_kernel, and its PPO gradient, te_policy_ppo_grad
+// (te_policy_grad.hpp); none is part of te_step.
 //
 // Reference citations are file:line under the reference's src/ tree.
 #include <hip/hip_runtime.h>
@@ -844,18 +845,43 @@ __global__ __launch_bounds__(256) void ally_patch_kernel(Params p, float* __rest
   d[0] = __uint_as_float(scratch[(size_t)(2 * j + 1) * p.Npad + env]); d[TE_LIDAR_CELLS] = (float)(w >> 16) / 5.0f;
   if (p.cfg.lidar_channels != 2) d[2 * TE_LIDAR_CELLS] = 0.1f;
 }
-// exp05: pursuer.drive(action) of drive_lw_rl_agent (exp05_vFinal_task.py:255-260; quadcopter.py:379-413) for armed allies
-__global__ __launch_bounds__(256) void set_ally_actions_kernel(Params p, int me, const float* __restrict__ actions) {
-  const int env = blockIdx.x * 256 + threadIdx.x;
-  if (env >= p.N) return;
-  const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
-  if (!v.gi(TE_D_ARMED, me)) return;
-  const float4 a = reinterpret_cast<const float4*>(actions)[env];
+// exp05: pursuer.drive(action) of drive_lw_rl_agent (exp05_vFinal_task.py:255-260; quadcopter.py:379-413) for an armed pursuer
+// `me` of env v: the velocity command, the set-point, and the action remembered as the pursuer's last action.
+TE_DEV void drive_caller_pursuer(const GView& v, int me, float4 a) {
   float vx, vy, vz;
   command_to_velocity(a.x, a.y, a.z, a.w, vx, vy, vz);
   v.sf(TE_X_CMD + 0, me, vx); v.sf(TE_X_CMD + 1, me, vy); v.sf(TE_X_CMD + 2, me, vz);
   v.sf(TE_D_SETPOINT + 0, me, vx); v.sf(TE_D_SETPOINT + 1, me, vy); v.sf(TE_D_SETPOINT + 2, me, 0.0f); v.sf(TE_D_SETPOINT + 3, me, vz);
   v.sf(TE_D_ALLY_ACTION + 0, me, a.x); v.sf(TE_D_ALLY_ACTION + 1, me, a.y); v.sf(TE_D_ALLY_ACTION + 2, me, a.z); v.sf(TE_D_ALLY_ACTION + 3, me, a.w);
+}
+
+__global__ __launch_bounds__(256) void set_ally_actions_kernel(Params p, int me, const float* __restrict__ actions) {
+  const int env = blockIdx.x * 256 + threadIdx.x;
+  if (env >= p.N) return;
+  const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
+  if (!v.gi(TE_D_ARMED, me)) return;
+  drive_caller_pursuer(v, me, reinterpret_cast<const float4*>(actions)[env]);
+}
+
+// te_drive_wingman: the deterministic predict of the packed policy on pursuer `me`'s observation (te_observe_wingman's output,
+// read as te_policy_act reads its rows), then set_ally_actions_kernel's drive with the clamped mean.  pol_forward is the one
+// policy_act_kernel runs, so mu is bitwise te_policy_act's.  Every row is computed; rows of envs whose pursuer is dead keep
+// their state (the reference does not call predict for them), mu is written for all rows.
+template <int C>
+__global__ __launch_bounds__(kPolThreads) void policy_drive_kernel(PolicyParams P, PolicyIn in, Params p, int me, float* __restrict__ mu) {
+  extern __shared__ __attribute__((aligned(16))) float pol_lds[];
+  const int tid = threadIdx.x, env = blockIdx.x * kPolTileM + tid;
+  pol_forward<C>(P, in, pol_lds, blockIdx.x * kPolTileM, PolNoSave{});
+  if (tid >= kPolTileM || env >= in.n) return;
+  const float* MU = pol_mu_lds(pol_lds) + tid * 4;   // read back by the thread that computed it
+  if (mu) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) mu[(size_t)env * 4 + a] = MU[a];
+  }
+  const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
+  if (!v.gi(TE_D_ARMED, me)) return;
+  drive_caller_pursuer(v, me, make_float4(fmaxf(fminf(MU[0], 1.f), -1.f), fmaxf(fminf(MU[1], 1.f), -1.f), fmaxf(fminf(MU[2], 1.f), -1.f),
+                                          fmaxf(fminf(MU[3], 1.f), 0.f)));
 }
 
 // te_observe: current observation without stepping
@@ -1851,6 +1877,34 @@ __attribute__((visibility("default"))) int te_policy_act(const float* params, in
   const dim3 grid((unsigned)((n + kPolTileM - 1) / kPolTileM));
   if (lidar_channels == 3) hipLaunchKernelGGL(policy_act_kernel<3>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, io);
   else hipLaunchKernelGGL(policy_act_kernel<2>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, io);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_drive_wingman(te_env* e, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar,
+                                                            float* inertial, float* last_action, float* mu, void* stream) {
+  if (!e) return fail("te_drive_wingman: null env");
+  if (!wingman_is_callers(e, wingman))
+    return fail("te_drive_wingman: this pursuer is not driven by the caller (exp05: cfg.ally_policy == TE_ALLY_EXTERNAL, pursuer 1; evaluation: the driver mask in cfg.evaluation)");
+  if (!params || !lidar || !inertial || !last_action) return fail("te_drive_wingman: params, lidar, inertial and last_action are required");
+  if (lidar_channels != e->p.cfg.lidar_channels)
+    return fail("te_drive_wingman: lidar_channels (" + std::to_string(lidar_channels) + ") differs from the env's cfg.lidar_channels (" +
+                std::to_string(e->p.cfg.lidar_channels) + ")");
+  if ((uintptr_t)params & 15) return fail("te_drive_wingman: params must be 16-byte aligned");
+  if (((uintptr_t)lidar & 15) || ((uintptr_t)last_action & 15)) return fail("te_drive_wingman: lidar and last_action must be 16-byte aligned");
+  if (((uintptr_t)inertial & 3) || ((uintptr_t)mu & 3)) return fail("te_drive_wingman: inertial and mu must be 4-byte aligned");
+  DeviceGuard guard(e->device);
+  static uint64_t opted[2] = {0, 0};
+  if (policy_lds_opt_in(lidar_channels == 3 ? reinterpret_cast<const void*>(&policy_drive_kernel<3>) : reinterpret_cast<const void*>(&policy_drive_kernel<2>),
+                        opted[lidar_channels - 2]))
+    return 1;
+  if (te_observe_wingman(e, wingman, lidar, inertial, last_action, nullptr, stream)) return 1;
+  PolicyParams P = policy_layout(lidar_channels);
+  P.base = params;
+  const PolicyIn in{lidar, inertial, last_action, nullptr, e->p.N};
+  const dim3 grid((unsigned)((e->p.N + kPolTileM - 1) / kPolTileM));
+  if (lidar_channels == 3) hipLaunchKernelGGL(policy_drive_kernel<3>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, in, e->p, (int)wingman, mu);
+  else hipLaunchKernelGGL(policy_drive_kernel<2>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, in, e->p, (int)wingman, mu);
   TE_HIP(hipGetLastError());
   return 0;
 }

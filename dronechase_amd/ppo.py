@@ -17,13 +17,16 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
     instead of ~40 PyTorch launches per step;
   * PPOConfig.fused_update: the minibatch's loss gradient in one ABI call (te_policy_ppo_grad, FusedPolicy.ppo_grad) instead of
     the PyTorch forward + autograd, reading the rollout rows through the minibatch index (no gather of the observations);
+  * PPOConfig.wingman_driver / PPO(wingman_policy=...): exp05's ally (and the evaluation task's "nn" drivers) flown by a frozen
+    policy inside the rollout, one te_drive_wingman call per caller-driven pursuer before every te_step;
   * multi-GPU: one process per GPU, each with its own env shard; gradients are averaged with
     torch.distributed all_reduce (RCCL) — the only collective of the whole system, once per minibatch.
 """
 from __future__ import annotations
 
+import copy
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import ctypes as C
 
@@ -110,6 +113,19 @@ class FusedPolicy:
 
     def refresh(self) -> None:
         pack_policy(self.policy, out=self.params)
+
+    @torch.no_grad()
+    def load_from(self, module: nn.Module) -> None:
+        """Copy `module`'s weights into this object's policy and repack them in place: the packed buffer keeps its address, so a
+        HIP graph that captured a call flies the new weights.  A frozen snapshot of a learner is FusedPolicy(copy.deepcopy(learner))
+        re-synced with load_from(learner)."""
+        src, dst = _packed_order(module), _packed_order(self.policy)
+        if len(src) != len(dst) or any(a.shape != b.shape for a, b in zip(src, dst)):
+            raise ValueError("FusedPolicy.load_from: the module's parameters do not match this policy's layout")
+        if module is not self.policy:
+            for a, b in zip(src, dst):
+                b.copy_(a)
+        self.refresh()
 
     def ppo_grad(self, obs: Dict[str, torch.Tensor], index: Optional[torch.Tensor], action: torch.Tensor, old_logp: torch.Tensor,
                  adv: torch.Tensor, ret: torch.Tensor, adv_mean_std: Optional[torch.Tensor], clip: float, vf_coef: float,
@@ -247,6 +263,13 @@ class PPOConfig:
     # Off by default: the gradient agrees with autograd's to a tolerance (another summation order), not bit for bit
     fused_update: bool = False
     reward_scale: float = 1e-3   # rewards reach +-1000 (exp03_vFinal_task.py:423-515); SB3 users wrap VecNormalize
+    # who flies the caller-driven pursuers of the env (exp05's ally, the pursuers of cfg.evaluation's driver mask) during collect():
+    # "none" = nobody, and PPO refuses such an env unless PPO(..., wingman_policy=module) gives a frozen policy to fly them;
+    # "snapshot" = a frozen copy of the learner (bo_exp05_vFinal_home_office_app.py:140-175: update_model_path after every training
+    # chunk), re-synced at the start of the first collect() after every wingman_sync_every updates.  Either way one te_drive_wingman
+    # call per pursuer (observe, deterministic forward, clamp, drive) runs before every te_step, in both collect paths
+    wingman_driver: str = "none"
+    wingman_sync_every: int = 1
 
 
 class RolloutBuffer:
@@ -282,18 +305,44 @@ class RolloutBuffer:
         self.ret.copy_(self.adv + self.values)
 
 
-class PPO:
-    """`env` is a dronechase_amd.batched_env.BatchedEnv (classic own-sphere observation)."""
+def caller_driven_pursuers(ecfg) -> List[int]:
+    """The pursuers of an env config that the caller flies (te_observe_wingman / te_set_wingman_actions): pursuer 1 of exp05
+    (cfg.ally_policy == TE_ALLY_EXTERNAL) and every pursuer whose bit is set in cfg.evaluation's driver mask (bits 8..)."""
+    if ecfg is None:
+        return []
+    mask = (int(ecfg.evaluation) & 0xFFFFFFFF) >> 8
+    return [p for p in range(int(ecfg.n_pursuers)) if (int(ecfg.ally_policy) == 3 and p == 1) or (mask >> p) & 1]
 
-    def __init__(self, env, cfg: Optional[PPOConfig] = None, policy: Optional[nn.Module] = None, seed: int = 0):
+
+class PPO:
+    """`env` is a dronechase_amd.batched_env.BatchedEnv (classic own-sphere observation).  An env with caller-driven pursuers
+    (exp05, the evaluation task's driver mask) needs PPOConfig.wingman_driver = "snapshot" or a frozen `wingman_policy`."""
+
+    def __init__(self, env, cfg: Optional[PPOConfig] = None, policy: Optional[nn.Module] = None, seed: int = 0,
+                 wingman_policy: Optional[nn.Module] = None):
         self.env, self.cfg = env, cfg or PPOConfig()
         self.device = env.device
         ecfg = getattr(env, "cfg", None)
-        if ecfg is not None and (int(ecfg.ally_policy) == 3 or (int(ecfg.evaluation) >> 8) != 0):
+        self.wingmen = caller_driven_pursuers(ecfg)
+        drv = self.cfg.wingman_driver
+        if drv not in ("none", "snapshot"):
+            raise ValueError(f"PPOConfig.wingman_driver must be 'none' or 'snapshot', not {drv!r}")
+        caller_driven = ecfg is not None and (int(ecfg.ally_policy) == 3 or (int(ecfg.evaluation) >> 8) != 0)
+        if caller_driven and drv == "none" and wingman_policy is None:
             # exp05 / Evaluation_Task "nn" drivers: somebody has to answer te_observe_wingman with te_set_wingman_actions
             # before every te_step; this rollout loop does not, and the wingman would fly a stale set-point
             raise ValueError("PPO drives the agent only: an environment with caller-driven wingmen (exp05, evaluation driver mask) "
                              "needs its wingman driver in the loop (ThreatEngageVecEnv.update_model), not this rollout")
+        if drv != "none" or wingman_policy is not None:
+            if not self.wingmen:
+                raise ValueError("PPO: a wingman driver was given, but this environment has no caller-driven pursuer "
+                                 "(exp05's ally or cfg.evaluation's driver mask)")
+            if drv == "snapshot" and wingman_policy is not None:
+                raise ValueError("PPO: wingman_driver='snapshot' flies a copy of the learner; pass wingman_policy with wingman_driver='none'")
+            if self.device.type != "cuda":
+                raise ValueError("PPO's wingman driver runs the HIP kernels of te_drive_wingman: it needs a GPU device")
+            if int(self.cfg.wingman_sync_every) < 1:
+                raise ValueError("PPOConfig.wingman_sync_every must be >= 1")
         torch.manual_seed(seed)
         self.policy = (policy or LidarInertialActionPolicy(lidar_shape=tuple(env.lidar.shape[1:]))).to(self.device)
         fused = bool(self.cfg.fast_learner) and self.device.type == "cuda"
@@ -306,6 +355,21 @@ class PPO:
         if self.distributed:  # same initial weights on every rank
             for p in self.policy.parameters():
                 torch.distributed.broadcast(p.data, src=0)
+        # the frozen policy of the caller-driven pursuers: never trained, no gradient.  Its packed buffer keeps its address
+        # (sync_wingmen repacks in place), so the captured rollout graph flies whatever was synced last
+        self.wingman, self._wingman_snapshot, self._updates_since_sync = None, False, 0
+        if self.wingmen:
+            if wingman_policy is None:
+                self._wingman_snapshot = True
+                wingman_policy = copy.deepcopy(self.policy).requires_grad_(False)
+            self.wingman = FusedPolicy(wingman_policy)
+            if self.wingman.device != self.device:
+                raise ValueError(f"PPO: wingman_policy lives on {self.wingman.device}, the environment on {self.device}")
+            if self.wingman.lidar_channels != int(ecfg.lidar_channels):
+                raise ValueError(f"PPO: wingman_policy reads {self.wingman.lidar_channels} LIDAR channels, the environment has {int(ecfg.lidar_channels)}")
+            self._wingman_mu = {w: torch.zeros((env.N, 4), device=self.device) for w in self.wingmen}   # the last drive's mean
+            for w in self.wingmen:
+                env.wingman_scratch(w)      # allocated now, not inside a graph capture
         # ONE gradient bucket: every parameter's .grad is a view of this flat buffer, so data-parallel training averages the
         # gradients of a minibatch with a single all-reduce (RCCL over xGMI: a ring is per-link bound, 25 small collectives per
         # minibatch would be latency-bound; the policy has ~0.3 M parameters = 1.2 MB, one bucket)
@@ -327,6 +391,19 @@ class PPO:
         self.direct = env.N % 2 == 0   # slot t of the LIDAR buffer starts on a 16-byte boundary (4 056 bytes per env)
         self._obs = None               # set by the first collect(): te_observe of the reset state
         self.num_timesteps = 0
+
+    def sync_wingmen(self) -> None:
+        """Repack the wingmen's frozen policy in place: the learner's current weights with wingman_driver='snapshot', the given
+        wingman_policy's otherwise (after the caller changed it)."""
+        if self.wingman is None:
+            raise ValueError("PPO.sync_wingmen: this PPO has no wingman driver")
+        self.wingman.load_from(self.policy if self._wingman_snapshot else self.wingman.policy)
+        self._updates_since_sync = 0
+
+    def _drive_wingmen(self) -> None:
+        """drive_lw_rl_agent of every caller-driven pursuer on the current state, before te_step (exp05_vFinal_task.py:252-260)."""
+        for w in self.wingmen:
+            self.env.drive_wingman(w, self.wingman, mu=self._wingman_mu[w])
 
     def _slot(self, t: int):
         b = self.buf
@@ -359,11 +436,12 @@ class PPO:
                 logp = (-0.5 * eps * eps - log_std - 0.9189385332046727).sum(-1)
                 a_env = torch.max(torch.min(a, self.high), self.low).contiguous()
             self._g["a"].copy_(a); self._g["logp"].copy_(logp); self._g["v"].copy_(v)
+            self._drive_wingmen()
             lidar, inertial, last_action, reward, done, _ = self.env.step(a_env, terminal=False)
             self._g["reward"].copy_(reward); self._g["done"].copy_(done)
             self._g_obs["lidar"].copy_(lidar); self._g_obs["inertial_data"].copy_(inertial); self._g_obs["last_action"].copy_(last_action)
 
-        state = self.env.get_state().clone()          # warm-up and capture must not advance the environments
+        state = self.env.get_state().clone()          # warm-up and capture must not advance the environments (nor move the wingmen's set-points)
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
@@ -402,6 +480,8 @@ class PPO:
     def collect(self) -> Dict[str, float]:
         if self.fused is not None:   # update() moved the module's weights: repack them into the buffer the captured graph reads
             self.fused.refresh()
+        if self._wingman_snapshot and self._updates_since_sync >= self.cfg.wingman_sync_every:
+            self.sync_wingmen()
         if self.cfg.use_graph and self.device.type == "cuda":
             return self._collect_graph()
         return self._collect_eager()
@@ -427,6 +507,7 @@ class PPO:
                 b.actions[t], b.logp[t], b.values[t] = a, dist.log_prob(a).sum(-1), v
                 a_env = torch.max(torch.min(a, self.high), self.low).contiguous()
             dest = self._slot(t + 1) if (self.direct and t + 1 < c.n_steps) else None
+            self._drive_wingmen()
             lidar, inertial, last_action, reward, done, _info = self.env.step(a_env, terminal=False, out=dest)
             if dest is None and t + 1 < c.n_steps:   # odd n_envs: the slots are not 16-byte aligned, copy instead
                 for k, src in zip(("lidar", "inertial_data", "last_action"), (lidar, inertial, last_action)):
@@ -483,6 +564,7 @@ class PPO:
                     acc += torch.stack((pg.detach(), vl.detach(), ent.detach(), ((ratio - 1).abs() > c.clip_range).float().mean()))
                 n_batches += 1
         pg_s, vl_s, ent_s, clip_s = (acc / max(n_batches, 1)).tolist()
+        self._updates_since_sync += 1
         return {"pg_loss": pg_s, "v_loss": vl_s, "entropy": ent_s, "clip_frac": clip_s}
 
     def _fused_minibatch(self, obs, idx, actions, old_logp, adv, ret) -> None:

@@ -371,6 +371,18 @@ int te_set_ally_actions(te_env* env, const float* ally_actions, void* stream);
  * one `self.last_action` between all "nn" drivers of an env, i.e. a wingman sees its predecessor's action: not restated). */
 int te_observe_wingman(te_env* env, int32_t wingman, float* lidar, float* inertial, float* last_action, uint8_t* active, void* stream);
 int te_set_wingman_actions(te_env* env, int32_t wingman, const float* actions, void* stream);
+/* Exp05_vFinal_Task.drive_lw_rl_agent for caller-driven pursuer `wingman`, with the packed LidarInertialActionPolicy `params`
+ * (te_policy_act's layout below, lidar_channels == cfg.lidar_channels) as the driver, deterministic:
+ *   te_observe_wingman(wingman) into lidar [N][C][13][26] / inertial [N][15] / last_action [N][4] (caller-owned scratch, same
+ *   alignment rules: lidar and last_action 16-byte aligned), then for every env whose pursuer `wingman` is armed:
+ *   action = clamp(mu, [-1,1]^3 x [0,1]) and exactly what te_set_wingman_actions does with it (velocity command, set-point,
+ *   remembered last action).  The env state afterwards is bitwise the one of te_observe_wingman -> te_policy_act (eps NULL)
+ *   -> clamp -> te_set_wingman_actions.
+ * mu (optional, [N][4], 4-byte aligned) receives the unclamped mean of every row, bitwise te_policy_act's.  params is 16-byte
+ * aligned.  Enqueues on `stream` only (no allocation, no host synchronisation: a HIP graph can capture it); every argument
+ * error returns before anything is launched. */
+int te_drive_wingman(te_env* env, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar, float* inertial,
+                     float* last_action, float* mu, void* stream);
 
 /* Evaluation_Task.compute_info (evaluation_task.py:553-574), cfg.evaluation only: wingman_info [N,P,5] i32 with the rows
  * (lw_kills, lw_alive, lw_munitions, current_wave, step) of every pursuer AFTER the last te_step (the reference lists the
