@@ -17,7 +17,7 @@ EXPORTS = (
     "te_config_default", "te_create", "te_destroy", "te_reset", "te_observe", "te_step", "te_random_actions",
     "te_state_words", "te_get_state", "te_set_state", "te_algorithmic_bytes_per_env_step", "te_profile_begin",
     "te_profile_end", "te_debug_stamps", "te_abi_version", "te_last_error", "te_step_stacked", "te_observe_stacked", "te_observe_ally", "te_set_ally_actions", "te_wingman_info", "te_calculate_rounds", "te_observe_wingman", "te_set_wingman_actions", "te_drive_wingman", "te_quad_preset", "te_step_students", "te_set_persistent_obs",
-    "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad",
+    "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad", "te_kernel_plan",
 )
 
 
@@ -64,6 +64,7 @@ def load() -> C.CDLL:
     L.te_get_state.argtypes = [vp, vp, C.c_size_t, vp]
     L.te_set_state.argtypes = [vp, vp, C.c_size_t, vp]
     L.te_algorithmic_bytes_per_env_step.argtypes = [C.POINTER(K.Config), C.POINTER(C.c_size_t)]
+    L.te_kernel_plan.argtypes = [C.POINTER(K.Config), C.c_char_p, C.c_size_t]
     L.te_debug_stamps.argtypes = [vp, C.POINTER(C.c_uint64), i32]
     L.te_profile_begin.argtypes = [vp, i32]
     L.te_set_persistent_obs.argtypes = [vp, i32]
@@ -96,6 +97,13 @@ def default_config(task, **overrides) -> K.Config:
         if load().te_quad_preset(C.byref(cfg), int(overrides.pop("quad_preset"))):
             raise ValueError("unknown quad_preset")
     return K.apply_overrides(cfg, **overrides)
+
+
+def kernel_plan(cfg: K.Config) -> dict:
+    """te_kernel_plan: {role: kernel name} that te_create would launch for `cfg` under the current TE_* environment knobs (no device needed)."""
+    buf = C.create_string_buffer(1024)
+    check(load().te_kernel_plan(C.byref(cfg), buf, len(buf)), "te_kernel_plan")
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
 
 def algorithmic_bytes_per_env_step(cfg: K.Config) -> int:

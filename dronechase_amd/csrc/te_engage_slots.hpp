@@ -27,10 +27,9 @@ namespace te {
 
 constexpr int kSlotWaves = 16;     // waves of a chunk's workgroup = drone slots served (1 024 threads)
 constexpr int kSlotPursuers = 4;   // pursuers served (the exp tasks have 2)
-// te_create's default: every shard size takes the slot waves since dead-slot waves retire early (round 4: stage03 x 65 536, driver's window
-// 18.4 vs 21.6 us, steady state and all-armed a tie; x 32 768: 14.2 vs 20.1; x 8 192: 10.4 vs 16.9 us; profiles/r04_j_ab_engage_slots_v4.txt);
-// TE_ENGAGE=regs brings engage_kernel back, and a te_env above this many (env, slot) pairs keeps it
-constexpr long long kSlotsMaxPairs = 1ll << 40;
+// te_create's default at every shard size, since dead-slot waves retire early (round 4: stage03 x 65 536, driver's window 18.4 vs 21.6 us,
+// steady state and all-armed a tie; x 32 768: 14.2 vs 20.1; x 8 192: 10.4 vs 16.9 us; profiles/r04_j_ab_engage_slots_v4.txt); TE_ENGAGE=regs
+// brings engage_kernel back
 
 struct SlotRows {  // LDS rows of 64 words
   int D, P;
@@ -60,10 +59,10 @@ enum : uint32_t { SLOT_HIT = 1u << 8, SLOT_EXPLODE = 1u << 9, SLOT_SUICIDE = 1u 
 #define TE_WSTAMP(idx, wait) do {} while (0)
 #endif
 
-// WPE: waves per SIMD the register budget is held to.  6 (75 VGPRs) by default; 8 (64 VGPRs, 24 B of scratch; TE_SLOT_WPE8=1) keeps one more
-// workgroup per CU in the heavy regimes of a large shard (steady-state engage 29.5 -> 26.2 us at 65 536 envs) and costs the light ones 1 us.
-template <int DM, int WPE = 6>
-__global__ __launch_bounds__(DM * 64) __attribute__((amdgpu_waves_per_eu(WPE, WPE > 6 ? WPE : 10))) void engage_slots_kernel(Params p, const float* __restrict__ actions, StepOut o) {
+// The register budget is held to 6 waves per SIMD (75 VGPRs).  A 64-VGPR build (8 waves, 24 B of scratch) kept one more workgroup per CU in the
+// heavy regimes of a large shard (steady-state engage 29.5 -> 26.2 us at 65 536 envs) but cost the light ones 1 us.
+template <int DM>
+__global__ __launch_bounds__(DM * 64) __attribute__((amdgpu_waves_per_eu(6, 10))) void engage_slots_kernel(Params p, const float* __restrict__ actions, StepOut o) {
   TE_EXACT
   extern __shared__ uint32_t sm[];
   const te_config& c = p.cfg;

@@ -55,7 +55,7 @@ namespace te {
 //   [drone waves] wave = slot * (Npad/64) + chunk, SLOT-major: the always-armed slots (agent, allies, the first
 //                 invaders of the current round) reach the SIMDs first, the mostly disarmed slots retire after
 //                 one load.  Chunk-major order let ~6 000 disarmed waves take the issue slots first.
-// Measured on stage03, 65 536 envs (tools/k1_phase.py): chunk-major + per-wave fill 82-93 us; this order 53-71 us.
+// Measured on stage03, 65 536 envs: chunk-major + per-wave fill 82-93 us; this order 53-71 us.
 #ifndef TE_K1_BLOCK
 #define TE_K1_BLOCK 64
 #endif
@@ -78,7 +78,7 @@ constexpr long long kHelpMaxPairs = 98304;
 typedef float te_f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t te_u4 __attribute__((ext_vector_type(4)));
 #define TE_FILL_STORE(ptr) __builtin_nontemporal_store((te_f4){1.0f, 1.0f, 1.0f, 1.0f}, reinterpret_cast<te_f4*>(ptr))
-// mode 0 / 1 / 2: stream ones over the whole buffer (pointer loop / scalar buffer loop / + s_setprio).  mode 3 (persistent observation,
+// mode 0 / 1: stream ones over the whole buffer (pointer loop for buffers beyond the buffer descriptor's reach / scalar buffer loop).  mode 3 (persistent observation,
 // te_set_persistent_obs): the buffer still holds the previous observation; wave w = list * nchunks + chunk sets the cells that observation
 // patched in output sphere `list` (= observer * 6 + sphere) of the chunk's 64 envs back to one — scattered stores that ride on the flights
 // of the same launch (which leave HBM idle) instead of sitting in the stacked-observation launch's critical path.
@@ -392,7 +392,6 @@ __global__ __launch_bounds__(HELP ? 128 : TE_K1_BLOCK) TE_K1_ATTR void substeps_
         // Scalar loop: one buffer store per 1 KB block, the block offset in an SGPR.  The pointer form below costs three VALU
         // instructions per store (64-bit address, index, compare), and next to five or six flights on the same SIMD every one of them
         // queues behind the flights' VALU work: the background then finishes 10-20 us after the last flight (tools/k1_waves.py).
-        if (fill.mode >= 2) __builtin_amdgcn_s_setprio(3);
         const uint32_t n_blocks = fill.total_quads >> 6;   // whole 1 KB blocks
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(fill.lidar, 0, (int)(n_blocks << 10), 0x00020000);
         const int voff = lane * 16;
@@ -960,24 +959,186 @@ __global__ void random_actions_kernel(Params p, float* __restrict__ actions, uin
 // ==============================================================================================
 using namespace te;
 
+// ---- Kernel plan: the kernels a te_env launches, chosen once from its config (plan_kernels).  One launch role: the kernel, its name as
+// rocprofv3 prints it (without the namespace and the signature), its workgroup and its dynamic LDS; the grid is sized per call.
+template <typename... Args> struct Launch { void (*fn)(Args...) = nullptr; const char* name = ""; unsigned block = 0; size_t lds = 0; };
+#define TE_KERNEL(...) &__VA_ARGS__, #__VA_ARGS__   // a kernel and its name: template arguments written out in full, defaults included
+
+struct KernelPlan {
+  Launch<Params, const float*, FillJob> substeps[2];   // K1; [1]: with the fill (or erase) waves of the LIDAR background, [0]: without
+  Launch<Params, const float*, StepOut> engage;         // K2, every engage/observe form
+  Launch<StackParams> ring_push;                        // stacked observation: pushes the step's ring entries (none: stacked_kernel does)
+  Launch<StackParams, StackOut> stack_view;             // stacked observation: stack_view_kernel or stacked_kernel
+  size_t observe_lds = 0;                               // observe_kernel
+  bool records_cells = false;   // the kernel that patches the LIDAR observation records the cells (te_set_persistent_obs); the LDS fallbacks do not
+  int n_fill_waves = 256, dense_min = kDenseMin;
+};
+static int family_of(int task) {
+  return task == TE_TASK_STAGE01 ? FAM_STAGE01 : (task == TE_TASK_STAGE02 ? FAM_STAGE02 : FAM_LEVEL4);
+}
+template <typename F>
+static void launch_by_family(int family, F&& f) {
+  switch (family) {
+    case FAM_STAGE01: f(std::integral_constant<int, FAM_STAGE01>{}); break;
+    case FAM_STAGE02: f(std::integral_constant<int, FAM_STAGE02>{}); break;
+    default: f(std::integral_constant<int, FAM_LEVEL4>{}); break;
+  }
+}
+template <typename F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <int FAMILY, bool NOISE, bool FILL, bool CES, bool HELP>
+static Launch<Params, const float*, FillJob> substep_role(const te_config& c) {
+  static const std::string name = "substeps_kernel<" + std::to_string(FAMILY) + (NOISE ? ", true" : ", false") + (FILL ? ", true" : ", false") +
+                                  (CES ? ", true" : ", false") + (HELP ? ", true>" : ", false>");   // HELP: a noise-helper wave per flight block
+  return {&substeps_kernel<FAMILY, NOISE, FILL, CES, HELP>, name.c_str(), HELP ? 128u : (unsigned)TE_K1_BLOCK, HELP ? (size_t)c.substeps * 1024 + 16 : 0};
+}
+
+// te_create's checks of the config alone; nullptr when it passes
+static const char* check_config(const te_config* cfg) {
+  if (cfg->struct_size != sizeof(te_config)) return "te_create: te_config.struct_size mismatch (ABI skew)";
+  const int D = cfg->n_pursuers + cfg->n_invaders;
+  if (cfg->n_envs < 1) return "te_create: n_envs < 1";
+  if (cfg->n_pursuers < 1 || cfg->n_invaders < 1 || D > kMaxD64 || cfg->n_pursuers > 31) return "te_create: need 1 <= P <= 31, 1 <= I, P + I <= 64";
+  if (cfg->initial_invaders < 0 || cfg->invaders_per_round < 0) return "te_create: initial_invaders / invaders_per_round must not be negative";
+  if (cfg->substeps < 0 || cfg->substeps > 255) return "te_create: substeps out of range";
+  // substeps == 0: env.step() without physics (the IMU is read from the state as it is, then engagement / reward / termination /
+  // waves / observation as usual).  Used to replay the reference's task-logic fixtures on exactly their positions.
+  if (cfg->substeps == 0 && cfg->observe_lag != 0) return "te_create: substeps == 0 (no physics) needs observe_lag == 0";
+  if (cfg->task < TE_TASK_STAGE01 || cfg->task > TE_TASK_LEVEL5_FUSION) return "te_create: unknown task";
+  if (cfg->ground_contact && family_of(cfg->task) != FAM_LEVEL4) return "te_create: cfg.ground_contact is built for the level4 task family only";
+  if (cfg->evaluation && (((uint32_t)cfg->evaluation >> 8) >> cfg->n_pursuers) != 0u) return "te_create: cfg.evaluation's driver mask names a pursuer that does not exist";
+  if (cfg->evaluation && !(family_of(cfg->task) == FAM_LEVEL4 && cfg->ally_policy == TE_ALLY_BT && !cfg->stacked_obs))
+    return "te_create: cfg.evaluation (Evaluation_Task rules) is the level4 task family with behaviour-tree drivers and the own-sphere observation";
+  if (cfg->ally_policy == TE_ALLY_EXTERNAL && !(family_of(cfg->task) == FAM_LEVEL4 && cfg->n_pursuers == 2))
+    return "te_create: TE_ALLY_EXTERNAL (exp05) is the level4 task family with exactly 2 pursuers (exp05_vFinal_task.py:103)";
+  if (cfg->stacked_obs && family_of(cfg->task) != FAM_LEVEL4) return "te_create: stacked_obs needs a level4-family task";
+  if (cfg->task == TE_TASK_STAGE01 && !(cfg->n_pursuers == 2 && cfg->n_invaders == 1)) return "te_create: stage01 is 2 pursuers + 1 invader";
+  if (cfg->lidar_radius <= 0.0f || cfg->dome_radius <= 0.0f || cfg->max_speed <= 0.0f) return "te_create: radii / max_speed must be positive";
+  if (cfg->control_every_substep != 0 && cfg->control_every_substep != 1) return "te_create: control_every_substep is 0 or 1";
+  if (cfg->lidar_channels != 3 && cfg->lidar_channels != 2) return "te_create: lidar_channels is 3 (distance, flag, time) or 2 (distance, flag)";
+  if (cfg->lidar_channels == 2 && cfg->stacked_obs) return "te_create: the stacked observation (level5) always has 3 channels";
+  if (cfg->io_location != TE_IO_DEVICE && cfg->io_location != TE_IO_HOST) return "te_create: io_location is TE_IO_DEVICE or TE_IO_HOST";
+  if (cfg->io_location == TE_IO_HOST && (cfg->stacked_obs || cfg->ally_policy == TE_ALLY_EXTERNAL || ((uint32_t)cfg->evaluation >> 8) != 0u))
+    return "te_create: TE_IO_HOST serves te_reset / te_observe / te_step / te_random_actions / te_get_state / te_set_state; the stacked observation and caller-driven wingmen take device pointers";
+  if (cfg->drone_contact != 0 && cfg->drone_contact != 1) return "te_create: drone_contact is 0 or 1";
+  if (cfg->drone_contact && !(cfg->contact_radius > 0.0f)) return "te_create: contact_radius must be positive";
+  const size_t npad = ((size_t)cfg->n_envs + 63) / 64 * 64;
+  if ((size_t)(TE_DRONE_WORDS + TE_X_WORDS) * D * npad >= (1ull << 30)) return "te_create: n_envs * drones too large for one te_env (state planes are indexed with 32 bits); shard it";
+  return nullptr;
+}
+
+// The kernels of a te_env with config `c` (check_config passed), and the environment knobs that override the choice.
+// Host code only, no HIP call: te_kernel_plan reports it without a device.  nullptr, or the reason no kernel serves the config.
+// multi_lds_max: the dynamic LDS the multi-slot engage form may ask for (te_create plans again with 64 KB when the device refuses more).
+static const char* plan_kernels(const te_config& c, KernelPlan* out, size_t multi_lds_max = 160 * 1024) {
+  KernelPlan& k = *out = KernelPlan{};
+  const int P = c.n_pursuers, D = P + c.n_invaders, fam = family_of(c.task);
+  const long long chunks = (c.n_envs + 63) / 64;
+  const bool l4 = fam == FAM_LEVEL4, contact = c.drone_contact != 0;
+  const char* engage = getenv("TE_ENGAGE");   // lds | regs | slots (= the default)
+  const bool eng_lds = engage && !strcmp(engage, "lds"), eng_regs = engage && !strcmp(engage, "regs");
+  // ---- engage / observe.  The register kernels, one wave per chunk (te_engage.hpp): engage_kernel<PM, IM> (level4 family up to 7 + 30 drones),
+  // engage_stage02_kernel, engage_stage01_kernel.  Other shapes, and TE_ENGAGE=lds: engage_observe_kernel (LDS phases).
+  const bool regs_l4 = l4 && !eng_lds && P <= 7 && D <= 37;
+  const bool regs_s2 = fam == FAM_STAGE02 && !eng_lds && P <= 2 && D <= 10;
+  const bool regs_s1 = fam == FAM_STAGE01 && !eng_lds;
+  if (D > kMaxD && !(regs_l4 && c.stacked_obs))
+    return "te_create: more than 32 drones per env are served for the stacked-observation tasks only (te_step_stacked / te_step_students: stacked_obs, P <= 7, P + I <= 37)";
+  if ((c.agent_scripted || c.reward_model != TE_REWARD_EXP03 || !c.agent_death_terminates || c.initial_invaders != 1 || c.invaders_per_round != 1) && !regs_l4)
+    return "te_create: agent_scripted / reward_model / agent_death_terminates / the round rule are built into engage_kernel: the level4 task family with P <= 7 and P + I <= 37";
+  if (contact && !(regs_l4 && P <= 6 && D <= 18))
+    return "te_create: cfg.drone_contact is built into engage_kernel: the level4 task family with P <= 6 and P + I <= 18";
+#ifdef TE_DEBUG_STAMPS   // the stamp build leaves the contact variants out (the compiler rejects them next to the stamp stores)
+  if (contact) return "te_create: cfg.drone_contact is not served by the stamp build (TE_DEBUG_STAMPS leaves out the drone-contact engage kernels)";
+#endif
+  // one wave per (chunk, slot) instead of one wave per chunk: a shard with fewer chunks than the chip has SIMDs is one dependent chain per
+  // wave, and the chain is what the slot waves shorten (te_engage_slots.hpp); TE_ENGAGE=regs keeps engage_kernel
+  const bool slots = regs_l4 && !eng_regs && !c.stacked_obs && D <= kSlotWaves && P <= kSlotPursuers && c.reward_model == TE_REWARD_EXP03 && !contact;
+  // several slots per wave (engage_slots_multi_kernel): the level5 family (no own sphere; more drones than a workgroup has waves) and the level4
+  // family beyond 16 drones (level5_2bt: 2 + 30).  For the level5 family a large shard gets fewer, fatter waves: when the chip cannot hold every
+  // chunk's workgroup at once (256 CUs x 24 waves at <= 80 VGPRs) — level5 x 65 536 envs: nine-wave workgroups ran in two rounds, 35 us; six
+  // waves of three slots: 28 us
+  int spw = 0;   // slots per wave of engage_slots_multi_kernel; 0: not that form
+  const size_t multi_lds = (size_t)multi_slot_lds_rows(D, P, !c.stacked_obs) * 256;
+  if (regs_l4 && !eng_regs && (D <= 32 || (c.stacked_obs && D <= 3 * kSlotWaves)) && !contact && (c.stacked_obs || D > kSlotWaves || slots)) {
+    int s = D <= kSlotWaves ? 1 : D <= 2 * kSlotWaves ? 2 : 3;   // (beyond 32 drones — level5_fusion 36, level5_dumb 37 — the masks are 64 bits: <3, false, WIDE>)
+    const int spw_max = c.stacked_obs ? 3 : 2;
+    // (with the own sphere, on shapes one slot per wave serves too, engage_slots_kernel stays ahead at every size — stage03 x 65 536: 81.8 vs
+    // 86.2 us per step, x 32 768: 51.0 vs 53.1, profiles/r04_q_ab_slots_per_wave.txt: most of its eleven waves retire at once — TE_SLOT_SPW=2 forces the other)
+    while (c.stacked_obs && s < spw_max && chunks * ((D + s - 1) / s) > 256 * 24 && P <= (D + s) / (s + 1)) s += 1;
+    if (const char* v = getenv("TE_SLOT_SPW")) { const int n = atoi(v); if (n >= 1 && n <= spw_max && (D + n - 1) / n <= kSlotWaves) s = n; }
+    if (P <= (D + s - 1) / s && multi_lds <= multi_lds_max && (c.stacked_obs || s > 1)) spw = s;   // (one slot per wave with the own sphere: engage_slots_kernel)
+  }
+  const size_t lds = (size_t)lds_rows(D, P) * kEPB * sizeof(uint32_t), slot_lds = (size_t)slot_lds_rows(D, P) * 256;
+  const unsigned multi_block = spw ? 64u * (unsigned)((D + spw - 1) / spw) : 0u;
+  static_assert(kSlotWaves == 16 && kPushSplit == 4 && FAM_LEVEL4 == 0 && FAM_STAGE01 == 1 && FAM_STAGE02 == 2, "the kernel names below");
+  if (spw && D > 32) k.engage = {TE_KERNEL(engage_slots_multi_kernel<3, false, true>), multi_block, multi_lds};
+  else if (spw && !c.stacked_obs) k.engage = {TE_KERNEL(engage_slots_multi_kernel<2, true, false>), multi_block, multi_lds};
+  else if (spw == 1) k.engage = {TE_KERNEL(engage_slots_multi_kernel<1, false, false>), multi_block, multi_lds};
+  else if (spw == 2) k.engage = {TE_KERNEL(engage_slots_multi_kernel<2, false, false>), multi_block, multi_lds};
+  else if (spw == 3) k.engage = {TE_KERNEL(engage_slots_multi_kernel<3, false, false>), multi_block, multi_lds};
+  else if (regs_s2 && !eng_regs) k.engage = {TE_KERNEL(engage_slots_stage02_kernel<16>), 64u * D, slot_lds};   // stage02 in the slot-wave form
+  else if (slots) k.engage = {TE_KERNEL(engage_slots_kernel<16>), 64u * D, slot_lds};
+#ifndef TE_DEBUG_STAMPS   // the contact pass has its own instantiations: it would cost every launch ~150 VGPRs
+  else if (contact && P <= 2 && D <= 11) k.engage = {TE_KERNEL(engage_kernel<2, 9, true>), 64, 0};
+  else if (contact) k.engage = {TE_KERNEL(engage_kernel<6, 12, true>), 64, 0};
+#endif
+  else if (regs_l4 && P <= 2 && D <= 11) k.engage = {TE_KERNEL(engage_kernel<2, 9, false>), 64, 0};
+  else if (regs_l4 && P <= 6 && D <= 18) k.engage = {TE_KERNEL(engage_kernel<6, 12, false>), 64, 0};
+  else if (regs_l4) k.engage = {TE_KERNEL(engage_kernel<7, 30, false>), 64, 0};
+  else if (regs_s2) k.engage = {TE_KERNEL(engage_stage02_kernel<2, 8>), 64, 0};
+  else if (regs_s1) k.engage = {TE_KERNEL(engage_stage01_kernel), 64, 0};
+  // > 53 KB of LDS per block = at most two blocks per CU: run those with eight waves (level4 family only: D > 15)
+  else if (l4 && lds > 53 * 1024) k.engage = {TE_KERNEL(engage_observe_kernel<0, 512>), 512, lds};
+  else if (l4) k.engage = {TE_KERNEL(engage_observe_kernel<0, 256>), 256, lds};
+  else if (fam == FAM_STAGE01) k.engage = {TE_KERNEL(engage_observe_kernel<1, 256>), 256, lds};
+  else k.engage = {TE_KERNEL(engage_observe_kernel<2, 256>), 256, lds};
+  k.observe_lds = lds;
+  k.records_cells = !c.stacked_obs && (regs_l4 || regs_s2 || regs_s1);
+  // ---- sub-steps.  Noise-helper waves (substeps_kernel<..., HELP>): worth their issue slots only while SIMDs idle, i.e. on small shards
+  const bool help_ok = c.motor_noise && c.substeps >= 2 && c.substeps <= 48 && P <= kEagerP;   // (the helped flights request eagerly: fly<..., EAGER>)
+  // ... or, in the level4 family, where a rollout flies the pursuers and one or two invaders of the D slots, shards whose TYPICAL launch stays below
+  // ~1.25 flights per SIMD: with the eager requests the helped kernel is ahead up to 20 480 stage03 envs in the window after a reset (+ 5 %) and in
+  // the steady state (+ 7 %), and 6 % behind with every slot armed; a tie at 24 576, 8 % behind at 32 768 (profiles/r04_k_ab_help_mid_shards.txt)
+  const bool typical_light = l4 && chunks * std::min(D, P + 2) <= 1280;
+  bool help = help_ok && ((long long)c.n_envs * D <= kHelpMaxPairs || typical_light);
+  if (const char* v = getenv("TE_K1_HELP")) help = atoi(v) != 0 && help_ok;
+  launch_by_family(fam, [&](auto F) { with_bool(c.motor_noise != 0, [&](auto N) { with_bool(c.control_every_substep != 0, [&](auto C) { with_bool(help, [&](auto H) {
+    constexpr int kF = decltype(F)::value;
+    constexpr bool kN = decltype(N)::value, kC = decltype(C)::value, kH = decltype(H)::value;
+    if constexpr (kN || !kH) k.substeps[0] = substep_role<kF, kN, false, kC, kH>(c), k.substeps[1] = substep_role<kF, kN, true, kC, kH>(c);   // (HELP implies NOISE)
+  }); }); }); });
+  if (const char* v = getenv("TE_DENSE_MIN")) { const int n = atoi(v); if (n >= 1 && n <= 65) k.dense_min = n; }
+  // fill waves of the sub-step kernel: one per CU of an MI355X; two per CU for the six-sphere background of level5 (1.6 GB next to ~8 flight
+  // waves per SIMD: 128 / 256 / 512 / 1 024 / 2 048 waves -> 599 / 596 / 592 / 619 / 637 us per step with the scalar loop; stage03 loses
+  // 12 / 35 % with 512 / 1 024)
+  if (c.stacked_obs) k.n_fill_waves = 512;
+  if (const char* v = getenv("TE_FILL_WAVES")) { const int n = atoi(v); if (n >= 1 && n <= (1 << 20)) k.n_fill_waves = n; }
+  // ---- stacked observation: ring_push_kernel<DM> + stack_view_kernel<DM> (te_stackview.hpp) up to 37 drones; beyond, and TE_STACKED=lds,
+  // stacked_kernel (te_stacked.hpp)
+  if (c.stacked_obs) {
+    const char* stacked = getenv("TE_STACKED");
+    const int dm = stacked && !strcmp(stacked, "lds") ? 0 : D <= 18 ? 18 : D <= 37 ? 37 : 0;
+    // small shards: fewer push waves than SIMDs even after dealing each pair's binning over kPushSplit waves
+    bool split = dm == 18 && chunks * P * kPushSplit <= 4096;
+    if (const char* v = getenv("TE_PUSH_SPLIT")) split = dm == 18 && atoi(v) != 0;
+    const size_t view_lds = (size_t)view_lds_rows(D) * kEPB * sizeof(uint32_t);
+    if (dm == 18 && split) k.ring_push = {TE_KERNEL(ring_push_kernel<18, 4>), 64 * kPushSplit, (size_t)4 * 18 * 256};
+    else if (dm == 18) k.ring_push = {TE_KERNEL(ring_push_kernel<18, 1>), 64, 0};
+    else if (dm == 37) k.ring_push = {TE_KERNEL(ring_push_kernel<37, 1>), 64, 0};
+    if (dm == 18) k.stack_view = {TE_KERNEL(stack_view_kernel<18>), kViewThreads, view_lds};
+    else if (dm == 37) k.stack_view = {TE_KERNEL(stack_view_kernel<37>), kViewThreads, view_lds};
+    else k.stack_view = {TE_KERNEL(stacked_kernel), kStackThreads, (size_t)stack_lds_rows(D, P) * kEPB * sizeof(uint32_t)};
+    k.records_cells = dm != 0;
+  }
+  return nullptr;
+}
+
 struct te_env {
   Params p;
   int device;
   int family;
-  size_t lds_bytes;
-  size_t stack_lds_bytes = 0;  // stacked_kernel (level5)
-  int push_split = 0;          // 1 = ring_push_kernel<18, kPushSplit>: the binning of a (chunk, wingman) pair dealt over kPushSplit waves (small shards; TE_PUSH_SPLIT=0/1)
-  int stack_regs = 0;          // 18 / 37: ring_push_kernel<DM> + stack_view_kernel<DM> (te_stackview.hpp); 0: stacked_kernel (more than 37 drones, TE_STACKED=lds)
-  size_t view_lds_bytes = 0;
+  KernelPlan k;                // the kernels it launches (plan_kernels)
   size_t dbg_words = 0;       // diagnostic builds: length of p.dbg
-  int engage_regs = 0;         // 1 = engage_kernel<2, 9>, 2 = engage_kernel<6, 12> (level4 family), 3 = engage_stage02_kernel<2, 8>, 4 = engage_stage01_kernel (te_engage.hpp: the env in registers, one wave per
-                               // chunk); 0 = engage_observe_kernel (LDS phases): other shapes, stage01 / stage02, TE_ENGAGE=lds
-  int k1_help = 0;             // 1 = substeps_kernel<..., HELP>: a noise-helper wave next to every flight (small shards; TE_K1_HELP=0/1)
-  int engage_slots = 0;        // 1 = engage_slots_kernel / engage_slots_stage02_kernel (te_engage_slots.hpp: one wave per (chunk, slot)) instead of engage_kernel;
-                               // 2 = engage_slots_multi_kernel<slot_spw, own sphere> with slot_waves waves (level5 family, level5_2bt, large level4 shards); TE_ENGAGE=regs turns them off
-  int slot_spw = 1, slot_waves = 0; size_t slot_lds = 0;
-  int slot_wpe8 = 0;           // engage_slots_kernel<16, 8>: the 64-VGPR build, large shards (TE_SLOT_WPE8=0/1)
-  int k2_threads = 256;        // engage/observe kernel: 512 when its LDS allows only two blocks per CU
   float* zero_actions = nullptr;     // te_step_students: the [N,4] action batch nobody reads (every pursuer is scripted)
   uint32_t* ally_scratch = nullptr;  // te_observe_wingman: owner planes between its two launches (te_create allocates them when a wingman is caller-driven)
   // cfg.io_location == TE_IO_HOST: device staging of every I/O buffer of te_step / te_observe / te_reset / te_random_actions /
@@ -992,10 +1153,6 @@ struct te_env {
   } hs;
   std::vector<int32_t> done_idx;   // host I/O: the done envs of the step, and the host landing zone of their terminal rows
   std::vector<char> done_rows;
-  int fill_mode = 1;       // TE_FILL_MODE: 0 pointer loop, 1 scalar buffer loop, 2 + s_setprio 3
-  int n_fill_waves = 256;  // fill waves of the sub-step kernel: one per CU of an MI355X; two per CU for the six-sphere background of
-                           // level5 (1.6 GB next to ~8 flight waves per SIMD: 128 / 256 / 512 / 1 024 / 2 048 waves -> 599 / 596 / 592 / 619 / 637 us
-                           // per step with the scalar loop; stage03 loses 12 / 35 % with 512 / 1 024); TE_FILL_WAVES overrides
   // profiling (te_profile_begin / te_profile_end)
   std::vector<hipEvent_t> events;
   int prof_cap = 0, prof_used = 0;
@@ -1020,20 +1177,6 @@ struct DeviceGuard {
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-static int family_of(int task) {
-  return task == TE_TASK_STAGE01 ? FAM_STAGE01 : (task == TE_TASK_STAGE02 ? FAM_STAGE02 : FAM_LEVEL4);
-}
-
-template <typename F>
-static int launch_by_family(int family, F&& f) {
-  switch (family) {
-    case FAM_STAGE01: f(std::integral_constant<int, FAM_STAGE01>{}); break;
-    case FAM_STAGE02: f(std::integral_constant<int, FAM_STAGE02>{}); break;
-    default: f(std::integral_constant<int, FAM_LEVEL4>{}); break;
-  }
-  return 0;
-}
-
 static void launch_census(te_env* e, hipStream_t st) {
   launch_by_family(e->family, [&](auto fam) {
     hipLaunchKernelGGL((census_kernel<decltype(fam)::value>), dim3(e->p.Npad / 64), dim3(64), 0, st, e->p);
@@ -1054,15 +1197,26 @@ static bool host_io(const te_env* e) { return e && e->p.cfg.io_location == TE_IO
 #define TE_H2D(dst, src, bytes) do { if ((src) && (bytes)) TE_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyHostToDevice, st)); } while (0)
 #define TE_D2H(dst, src, bytes) do { if ((dst) && (bytes)) TE_HIP(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, st)); } while (0)
 
-// A launch whose start / stop events carry the dispatch's own begin / end timestamps (hipExtLaunchKernel); the arguments are converted to the
-// kernel's formal types first, as a <<<>>> launch would
+// One launch of a plan entry.  Start / stop events, if given, carry the dispatch's own begin / end timestamps.  The arguments are converted
+// to the kernel's formal types first, as a <<<>>> launch would.
 template <typename... Formals, typename... Actuals>
-static void launch_timed(void (*kernel)(Formals...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, hipEvent_t start, hipEvent_t stop, Actuals&&... actuals) {
+static void launch(const Launch<Formals...>& k, unsigned grid, hipStream_t st, hipEvent_t start, hipEvent_t stop, Actuals&&... actuals) {
   static_assert(sizeof...(Formals) == sizeof...(Actuals), "argument count");
   std::tuple<Formals...> held{std::forward<Actuals>(actuals)...};
   void* ptrs[sizeof...(Formals)];
   std::apply([&](auto&... a) { int i = 0; ((ptrs[i++] = (void*)&a), ...); }, held);
-  (void)hipExtLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, ptrs, lds, st, start, stop, 0);
+  const void* fn = reinterpret_cast<const void*>(k.fn);
+  if (start || stop) (void)hipExtLaunchKernel(fn, dim3(grid), dim3(k.block), ptrs, k.lds, st, start, stop, 0);
+  else (void)hipLaunchKernel(fn, dim3(grid), dim3(k.block), ptrs, k.lds, st);
+}
+
+static hipError_t set_lds_limits(const KernelPlan& k) {   // dynamic LDS beyond the default 64 KB, on exactly the kernels of the plan
+  const std::pair<const void*, size_t> kernels[] = {{(const void*)k.engage.fn, k.engage.lds}, {(const void*)k.substeps[0].fn, k.substeps[0].lds},
+      {(const void*)k.substeps[1].fn, k.substeps[1].lds}, {(const void*)k.ring_push.fn, k.ring_push.lds}, {(const void*)k.stack_view.fn, k.stack_view.lds},
+      {(const void*)&observe_kernel, k.observe_lds}};
+  for (const auto& [fn, lds] : kernels)
+    if (hipError_t err = fn && lds ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess; err != hipSuccess) return err;
+  return hipSuccess;
 }
 
 extern "C" {
@@ -1071,33 +1225,8 @@ __attribute__((visibility("default"))) const char* te_last_error(void) { return 
 
 __attribute__((visibility("default"))) int te_create(const te_config* cfg, int32_t device_id, te_env** out) {
   if (!cfg || !out) return fail("te_create: null argument");
-  if (cfg->struct_size != sizeof(te_config)) return fail("te_create: te_config.struct_size mismatch (ABI skew)");
+  if (const char* why = check_config(cfg)) return fail(why);
   const int D = cfg->n_pursuers + cfg->n_invaders;
-  if (cfg->n_envs < 1) return fail("te_create: n_envs < 1");
-  if (cfg->n_pursuers < 1 || cfg->n_invaders < 1 || D > kMaxD64 || cfg->n_pursuers > 31) return fail("te_create: need 1 <= P <= 31, 1 <= I, P + I <= 64");
-  if (cfg->initial_invaders < 0 || cfg->invaders_per_round < 0) return fail("te_create: initial_invaders / invaders_per_round must not be negative");
-  if (cfg->substeps < 0 || cfg->substeps > 255) return fail("te_create: substeps out of range");
-  // substeps == 0: env.step() without physics (the IMU is read from the state as it is, then engagement / reward / termination /
-  // waves / observation as usual).  Used to replay the reference's task-logic fixtures on exactly their positions.
-  if (cfg->substeps == 0 && cfg->observe_lag != 0) return fail("te_create: substeps == 0 (no physics) needs observe_lag == 0");
-  if (cfg->task < TE_TASK_STAGE01 || cfg->task > TE_TASK_LEVEL5_FUSION) return fail("te_create: unknown task");
-  if (cfg->ground_contact && family_of(cfg->task) != FAM_LEVEL4) return fail("te_create: cfg.ground_contact is built for the level4 task family only");
-  if (cfg->evaluation && (((uint32_t)cfg->evaluation >> 8) >> cfg->n_pursuers) != 0u) return fail("te_create: cfg.evaluation's driver mask names a pursuer that does not exist");
-  if (cfg->evaluation && !(family_of(cfg->task) == FAM_LEVEL4 && cfg->ally_policy == TE_ALLY_BT && !cfg->stacked_obs))
-    return fail("te_create: cfg.evaluation (Evaluation_Task rules) is the level4 task family with behaviour-tree drivers and the own-sphere observation");
-  if (cfg->ally_policy == TE_ALLY_EXTERNAL && !(family_of(cfg->task) == FAM_LEVEL4 && cfg->n_pursuers == 2))
-    return fail("te_create: TE_ALLY_EXTERNAL (exp05) is the level4 task family with exactly 2 pursuers (exp05_vFinal_task.py:103)");
-  if (cfg->stacked_obs && family_of(cfg->task) != FAM_LEVEL4) return fail("te_create: stacked_obs needs a level4-family task");
-  if (cfg->task == TE_TASK_STAGE01 && !(cfg->n_pursuers == 2 && cfg->n_invaders == 1)) return fail("te_create: stage01 is 2 pursuers + 1 invader");
-  if (cfg->lidar_radius <= 0.0f || cfg->dome_radius <= 0.0f || cfg->max_speed <= 0.0f) return fail("te_create: radii / max_speed must be positive");
-  if (cfg->control_every_substep != 0 && cfg->control_every_substep != 1) return fail("te_create: control_every_substep is 0 or 1");
-  if (cfg->lidar_channels != 3 && cfg->lidar_channels != 2) return fail("te_create: lidar_channels is 3 (distance, flag, time) or 2 (distance, flag)");
-  if (cfg->lidar_channels == 2 && cfg->stacked_obs) return fail("te_create: the stacked observation (level5) always has 3 channels");
-  if (cfg->io_location != TE_IO_DEVICE && cfg->io_location != TE_IO_HOST) return fail("te_create: io_location is TE_IO_DEVICE or TE_IO_HOST");
-  if (cfg->io_location == TE_IO_HOST && (cfg->stacked_obs || cfg->ally_policy == TE_ALLY_EXTERNAL || ((uint32_t)cfg->evaluation >> 8) != 0u))
-    return fail("te_create: TE_IO_HOST serves te_reset / te_observe / te_step / te_random_actions / te_get_state / te_set_state; the stacked observation and caller-driven wingmen take device pointers");
-  if (cfg->drone_contact != 0 && cfg->drone_contact != 1) return fail("te_create: drone_contact is 0 or 1");
-  if (cfg->drone_contact && !(cfg->contact_radius > 0.0f)) return fail("te_create: contact_radius must be positive");
   int ndev = 0;
   TE_HIP(hipGetDeviceCount(&ndev));
   if (ndev < 1) return fail("te_create: no HIP device visible; this library has no CPU fallback");
@@ -1115,94 +1244,18 @@ __attribute__((visibility("default"))) int te_create(const te_config* cfg, int32
     hipError_t e_ = (x);                                                                               \
     if (e_ != hipSuccess) return bail(std::string("te_create: " #x ": ") + hipGetErrorString(e_));      \
   } while (0)
+  if (const char* why = plan_kernels(*cfg, &e->k)) return bail(why);
   e->family = family_of(cfg->task);
   e->p.cfg = *cfg;
   e->p.kd = derive(*cfg);
   e->p.N = cfg->n_envs; e->p.D = D; e->p.Npad = (cfg->n_envs + 63) / 64 * 64;
-  e->lds_bytes = (size_t)lds_rows(D, cfg->n_pursuers) * kEPB * sizeof(uint32_t);
-  if (e->family == FAM_LEVEL4) {
-    if (cfg->n_pursuers <= 2 && D <= 11) e->engage_regs = 1;
-    else if (cfg->n_pursuers <= 6 && D <= 18) e->engage_regs = 2;
-    else if (cfg->n_pursuers <= 7 && D <= 37) e->engage_regs = 5;
-  } else if (e->family == FAM_STAGE02) {
-    if (cfg->n_pursuers <= 2 && D <= 10) e->engage_regs = 3;
-  } else if (e->family == FAM_STAGE01) e->engage_regs = 4;
-  if (const char* v = getenv("TE_ENGAGE")) { if (!strcmp(v, "lds")) e->engage_regs = 0; }
-  const bool regs_l4 = e->engage_regs == 1 || e->engage_regs == 2 || e->engage_regs == 5;
-  // one wave per (chunk, slot) instead of one wave per chunk: a shard with fewer chunks than the chip has SIMDs is one dependent chain per
-  // wave, and the chain is what the slot waves shorten (te_engage_slots.hpp); large shards keep engage_kernel (fewer instructions in total)
-  if (regs_l4 && !cfg->stacked_obs && D <= kSlotWaves && cfg->n_pursuers <= kSlotPursuers && cfg->reward_model == TE_REWARD_EXP03 && !cfg->drone_contact) {
-    e->engage_slots = (long long)cfg->n_envs * D <= kSlotsMaxPairs ? 1 : 0;
-    if (const char* v = getenv("TE_ENGAGE")) { if (!strcmp(v, "slots")) e->engage_slots = 1; else if (!strcmp(v, "regs")) e->engage_slots = 0; }
+  e->p.dense_min = e->k.dense_min;
+  hipError_t le = set_lds_limits(e->k);
+  if (le != hipSuccess && e->k.engage.lds > 64 * 1024) {   // the device refuses a multi-slot engage form more than the default 64 KB (level5_2bt's
+    (void)hipGetLastError(); plan_kernels(*cfg, &e->k, 64 * 1024); le = set_lds_limits(e->k);   // 32 drones with {cell, range} rows): plan without it
   }
-  // several slots per wave (engage_slots_multi_kernel): the level5 family (no own sphere; more drones than a workgroup has waves) and the level4
-  // family beyond 16 drones (level5_2bt: 2 + 30).  For the level5 family a large shard gets fewer, fatter waves: when the chip cannot hold every
-  // chunk's workgroup at once (256 CUs x 24 waves at <= 80 VGPRs) — level5 x 65 536 envs: nine-wave workgroups ran in two rounds, 35 us; six
-  // waves of three slots: 28 us
-  if (regs_l4 && (D <= 32 || (cfg->stacked_obs && D <= 3 * kSlotWaves)) && !cfg->drone_contact && (cfg->stacked_obs || D > kSlotWaves || e->engage_slots == 1)) {
-    int spw = D <= kSlotWaves ? 1 : D <= 2 * kSlotWaves ? 2 : 3;   // (beyond 32 drones — level5_fusion 36, level5_dumb 37 — the masks are 64 bits: <3, false, WIDE>)
-    const long long chunks = (cfg->n_envs + 63) / 64;
-    const int spw_max = cfg->stacked_obs ? 3 : 2;
-    // (with the own sphere, on shapes one slot per wave serves too, engage_slots_kernel stays ahead at every size — stage03 x 65 536: 81.8 vs
-    // 86.2 us per step, x 32 768: 51.0 vs 53.1, profiles/r04_q_ab_slots_per_wave.txt: most of its eleven waves retire at once — TE_SLOT_SPW=2 forces the other)
-    while (cfg->stacked_obs && spw < spw_max && chunks * ((D + spw - 1) / spw) > 256 * 24 && cfg->n_pursuers <= (D + spw) / (spw + 1)) spw += 1;
-    if (const char* v = getenv("TE_SLOT_SPW")) { const int k = atoi(v); if (k >= 1 && k <= spw_max && (D + k - 1) / k <= kSlotWaves) spw = k; }
-    const int W = (D + spw - 1) / spw;
-    const size_t lds = (size_t)multi_slot_lds_rows(D, cfg->n_pursuers, !cfg->stacked_obs) * 256;
-    bool ok = cfg->n_pursuers <= W && lds <= 160 * 1024 && (cfg->stacked_obs || spw > 1);   // (one slot per wave with the own sphere: engage_slots_kernel)
-    if (const char* v = getenv("TE_ENGAGE")) { if (!strcmp(v, "regs")) ok = false; }
-    if (ok && lds > 64 * 1024) {   // beyond the default dynamic-LDS limit: level5_2bt's 32 drones with {cell, range} rows
-      const void* fn = cfg->stacked_obs ? (D > 32 ? (const void*)engage_slots_multi_kernel<3, false, true> : spw == 3 ? (const void*)engage_slots_multi_kernel<3, false> : spw == 2 ? (const void*)engage_slots_multi_kernel<2, false> : (const void*)engage_slots_multi_kernel<1, false>)
-                                        : (const void*)engage_slots_multi_kernel<2, true>;
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-    }
-    if (ok) { e->engage_slots = 2; e->slot_spw = spw; e->slot_waves = W; e->slot_lds = lds; }
-  }
-  // (opt-in: at 65 536 envs the 64-VGPR build is ahead once the rollout is heavy — steady state 679 -> 700 M env-steps/s — and behind in the
-  // light window right after a reset, which is the one the driver's bench times: 910 -> 890 M; profiles/r04_w_ab_slot_waves_64_vgprs.txt)
-  e->slot_wpe8 = 0;
-  if (const char* v = getenv("TE_SLOT_WPE8")) e->slot_wpe8 = e->engage_slots == 1 && e->family == FAM_LEVEL4 && atoi(v) != 0;
-  if (e->family == FAM_STAGE02 && e->engage_regs == 3) {   // stage02 in the same form (engage_slots_stage02_kernel)
-    e->engage_slots = (long long)cfg->n_envs * D <= kSlotsMaxPairs ? 1 : 0;
-    if (const char* v = getenv("TE_ENGAGE")) { if (!strcmp(v, "slots")) e->engage_slots = 1; else if (!strcmp(v, "regs")) e->engage_slots = 0; }
-  }
-  if (D > kMaxD && !(regs_l4 && cfg->stacked_obs))
-    return bail("te_create: more than 32 drones per env are served for the stacked-observation tasks only (te_step_stacked / te_step_students: stacked_obs, P <= 7, P + I <= 37)");
-  if ((cfg->agent_scripted || cfg->reward_model != TE_REWARD_EXP03 || !cfg->agent_death_terminates || cfg->initial_invaders != 1 || cfg->invaders_per_round != 1) && !regs_l4)
-    return bail("te_create: agent_scripted / reward_model / agent_death_terminates / the round rule are built into engage_kernel: the level4 task family with P <= 7 and P + I <= 37");
-  if (cfg->drone_contact && !(e->engage_regs == 1 || e->engage_regs == 2))
-    return bail("te_create: cfg.drone_contact is built into engage_kernel: the level4 task family with P <= 6 and P + I <= 18");
-  e->p.dense_min = kDenseMin;
-  // noise-helper waves (substeps_kernel<..., HELP>): worth their issue slots only while SIMDs idle, i.e. on small shards
-  const bool help_ok = cfg->motor_noise && cfg->substeps >= 2 && cfg->substeps <= 48 && cfg->n_pursuers <= kEagerP;   // (the helped flights request eagerly: fly<..., EAGER>)
-  // ... or, in the level4 family, where a rollout flies the pursuers and one or two invaders of the D slots, shards whose TYPICAL launch stays below
-  // ~1.25 flights per SIMD: with the eager requests the helped kernel is ahead up to 20 480 stage03 envs in the window after a reset (+ 5 %) and in
-  // the steady state (+ 7 %), and 6 % behind with every slot armed; a tie at 24 576, 8 % behind at 32 768 (profiles/r04_k_ab_help_mid_shards.txt)
-  const long long chunks_ = (cfg->n_envs + 63) / 64;
-  const bool typical_light = e->family == FAM_LEVEL4 && chunks_ * std::min(D, cfg->n_pursuers + 2) <= 1280;
-  e->k1_help = (help_ok && ((long long)cfg->n_envs * D <= kHelpMaxPairs || typical_light)) ? 1 : 0;
-  if (const char* v = getenv("TE_K1_HELP")) e->k1_help = (atoi(v) != 0 && help_ok) ? 1 : 0;
-  if (const char* v = getenv("TE_DENSE_MIN")) { int n = atoi(v); if (n >= 1 && n <= 65) e->p.dense_min = n; }
-  if (cfg->stacked_obs) e->n_fill_waves = 512;
-  if (const char* v = getenv("TE_FILL_MODE")) e->fill_mode = atoi(v);
-  if (const char* v = getenv("TE_FILL_WAVES")) { int n = atoi(v); if (n >= 1 && n <= (1 << 20)) e->n_fill_waves = n; }
-  {
-    hipError_t le = hipSuccess;
-    launch_by_family(e->family, [&](auto fam) {
-      le = hipFuncSetAttribute(reinterpret_cast<const void*>(&engage_observe_kernel<decltype(fam)::value>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes);
-    });
-    // > 53 KB of LDS per block = at most two blocks per CU: run those with eight waves (level4 family only: D > 15)
-    e->k2_threads = (e->family == FAM_LEVEL4 && e->lds_bytes > 53 * 1024) ? 512 : 256;
-    if (const char* v = getenv("TE_K2_THREADS")) { int n = atoi(v); if ((n == 256 || n == 512) && e->family == FAM_LEVEL4) e->k2_threads = n; }
-    if (le == hipSuccess && e->k2_threads == 512)
-      le = hipFuncSetAttribute(reinterpret_cast<const void*>(&engage_observe_kernel<FAM_LEVEL4, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes);
-    if (le == hipSuccess)
-      le = hipFuncSetAttribute(reinterpret_cast<const void*>(&observe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_bytes);
-    if (le != hipSuccess) return bail(std::string("te_create: this many drones per env needs more LDS than a workgroup may have: ") + hipGetErrorString(le));
-  }
+  if (le != hipSuccess) return bail(std::string("te_create: this many drones per env needs more LDS than a workgroup may have: ") + hipGetErrorString(le));
   const size_t dwords = (size_t)(TE_DRONE_WORDS + TE_X_WORDS) * D * e->p.Npad, ewords = (size_t)TE_ENV_WORDS * e->p.Npad;
-  if (dwords >= (1ull << 30)) return bail("te_create: n_envs * drones too large for one te_env (state planes are indexed with 32 bits); shard it");
   if (hipMalloc(&e->p.dstate, dwords * 4) != hipSuccess || hipMalloc(&e->p.estate, ewords * 4) != hipSuccess)
     return bail("te_create: hipMalloc failed");
   if (hipMalloc(&e->p.slot_mask, (size_t)(e->p.Npad / 64) * 8) != hipSuccess || hipMalloc(&e->p.live_mask, (size_t)(e->p.Npad / 64) * 8) != hipSuccess || hipMalloc(&e->p.mixed_count, (size_t)(e->p.Npad / 64) * 4) != hipSuccess ||
@@ -1241,20 +1294,10 @@ __attribute__((visibility("default"))) int te_create(const te_config* cfg, int32
     TE_HIP_OR_BAIL(hipMemsetAsync(e->zero_actions, 0, (size_t)e->p.Npad * 16, nullptr));
   }
   if (cfg->stacked_obs) {
-    e->stack_lds_bytes = (size_t)stack_lds_rows(D, cfg->n_pursuers) * kEPB * sizeof(uint32_t);
     const size_t snap_bytes = (size_t)snap_words(D, cfg->n_pursuers) * e->p.Npad * 4;
     const size_t ring_bytes = (size_t)cfg->n_envs * cfg->n_pursuers * TE_RING_DEPTH * e->p.entry_words * 4;
-    hipError_t le = hipFuncSetAttribute(reinterpret_cast<const void*>(&stacked_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->stack_lds_bytes);
-    e->stack_regs = D <= 18 ? 18 : (D <= 37 ? 37 : 0);
-    if (const char* v = getenv("TE_STACKED")) { if (!strcmp(v, "lds")) e->stack_regs = 0; }
-    // small shards: fewer push waves than SIMDs even after dealing each pair's binning over kPushSplit waves
-    e->push_split = e->stack_regs == 18 && (long long)((cfg->n_envs + 63) / 64) * cfg->n_pursuers * kPushSplit <= 4096 ? 1 : 0;
-    if (const char* v = getenv("TE_PUSH_SPLIT")) e->push_split = e->stack_regs == 18 && atoi(v) != 0;
-    e->view_lds_bytes = (size_t)view_lds_rows(D) * kEPB * sizeof(uint32_t);
-    if (le == hipSuccess && e->stack_regs == 18) le = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_view_kernel<18>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->view_lds_bytes);
-    if (le == hipSuccess && e->stack_regs == 37) le = hipFuncSetAttribute(reinterpret_cast<const void*>(&stack_view_kernel<37>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->view_lds_bytes);
-    if (le != hipSuccess || hipMalloc(&e->p.snap, snap_bytes) != hipSuccess || hipMalloc(&e->p.ring, ring_bytes) != hipSuccess)
-      return bail("te_create: stacked observation buffers (ring / snapshot / LDS) could not be set up");
+    if (hipMalloc(&e->p.snap, snap_bytes) != hipSuccess || hipMalloc(&e->p.ring, ring_bytes) != hipSuccess)
+      return bail("te_create: stacked observation buffers (ring / snapshot) could not be allocated");
     TE_HIP_OR_BAIL(hipMemsetAsync(e->p.snap, 0, snap_bytes, nullptr));
     TE_HIP_OR_BAIL(hipMemsetAsync(e->p.ring, 0, ring_bytes, nullptr));
   }
@@ -1276,6 +1319,18 @@ __attribute__((visibility("default"))) int te_create(const te_config* cfg, int32
   TE_HIP_OR_BAIL(hipStreamSynchronize(nullptr));
 #undef TE_HIP_OR_BAIL
   *out = e;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_kernel_plan(const te_config* cfg, char* out, size_t out_bytes) {
+  if (!cfg || !out) return fail("te_kernel_plan: null argument");
+  KernelPlan k;
+  const char* why = check_config(cfg);
+  if (why || (why = plan_kernels(*cfg, &k))) return fail(why);
+  std::string s = std::string("substeps=") + k.substeps[1].name + "\nsubsteps_nofill=" + k.substeps[0].name + "\nengage=" + k.engage.name + "\n" +
+                  (k.ring_push.fn ? std::string("ring_push=") + k.ring_push.name + "\n" : "") + (k.stack_view.fn ? std::string("stack_view=") + k.stack_view.name + "\n" : "");
+  if (s.size() >= out_bytes) return fail("te_kernel_plan: out_bytes too small (" + std::to_string(s.size() + 1) + " needed)");
+  memcpy(out, s.c_str(), s.size() + 1);
   return 0;
 }
 
@@ -1408,7 +1463,7 @@ static int observe_device(te_env* e, float* obs_lidar, float* obs_inertial, floa
   DeviceGuard guard(e->device);
   const int blocks = (e->p.N + kEPB - 1) / kEPB;
   if (obs_lidar && obs_lidar == e->last_stacked) e->last_stacked = nullptr;   // persistent observation: this call rewrites the buffer without recording
-  hipLaunchKernelGGL(observe_kernel, dim3(blocks), dim3(256), e->lds_bytes, (hipStream_t)stream, e->p, ObsOut{obs_lidar, obs_inertial, obs_last_action});
+  hipLaunchKernelGGL(observe_kernel, dim3(blocks), dim3(256), e->k.observe_lds, (hipStream_t)stream, e->p, ObsOut{obs_lidar, obs_inertial, obs_last_action});
   TE_HIP(hipGetLastError());
   return 0;
 }
@@ -1432,17 +1487,14 @@ static int step_impl(te_env* e, const float* actions, float* obs_lidar, size_t l
   // Profiling (te_profile_begin): 4 events per step.  Default: the kernels are launched with hipExtLaunchKernel, whose start / stop events
   // carry the dispatch's own begin / end timestamps (what rocprofv3 --kernel-trace reports): [0, 1] = the sub-step kernel, [2] = start of the
   // engage kernel, [3] = end of the step's last kernel.  TE_PROF=markers: round-2 form, marker packets between the launches (each bracket
-  // then includes ~5 us of queue time: tools/event_overhead_probe.py).
+  // then includes ~5 us of queue time).
   const bool prof = e->prof_used + 4 <= e->prof_cap;
   const bool prof_ext = prof && !e->prof_markers;
   hipEvent_t* pev = prof ? &e->events[e->prof_used] : nullptr;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;   // start / stop events of the next TE_LAUNCH
-#define TE_LAUNCH(K, grid, block, lds, ...) do { \
-    if (ev_a || ev_b) launch_timed(K, grid, block, lds, st, ev_a, ev_b, __VA_ARGS__); \
-    else hipLaunchKernelGGL(K, grid, block, lds, st, __VA_ARGS__); } while (0)
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;   // start / stop events of the next launch
+  const KernelPlan& k = e->k;
   if (prof && !prof_ext) TE_HIP(hipEventRecord(pev[0], st));
   const int waves = p.D * (p.Npad >> 6);
-  const bool noise = p.cfg.motor_noise != 0;
   // LIDAR background: N*1014 floats = quads float4 (+ <4 tail floats).  The drone waves write one float4 per
   // lane; the rest is split evenly over the fill waves.
   FillJob fill{nullptr, 0u, 0u, 0u, nullptr, 0u, 0u, 0u, 0u, 0u};
@@ -1450,15 +1502,15 @@ static int step_impl(te_env* e, const float* actions, float* obs_lidar, size_t l
   // persistent observation (te_set_persistent_obs): when this is the buffer the previous stacked observation went to, it still holds
   // ones + the recorded cells, and only those are touched (no background stream); otherwise fill as usual and record
   int persist = 0;
-  if (stack && e->persist_on && e->stack_regs && n_obs <= e->prev_observers) persist = (obs_lidar && obs_lidar == e->last_stacked && n_obs == e->last_n_obs) ? (n_obs > 1 ? 3 : 1) : 2;
-  if (!stack && e->persist_on && e->engage_regs && obs_lidar) persist = obs_lidar == e->last_stacked ? 1 : 2;   // te_step: the agent's own sphere
+  if (stack && e->persist_on && n_obs <= e->prev_observers) persist = (obs_lidar && obs_lidar == e->last_stacked && n_obs == e->last_n_obs) ? (n_obs > 1 ? 3 : 1) : 2;
+  if (!stack && e->persist_on && obs_lidar) persist = obs_lidar == e->last_stacked ? 1 : 2;   // te_step: the agent's own sphere
   if (obs_lidar && persist == 1) {   // the cells of the previous observation go back to one next to this launch's flights
     const uint32_t lists = stack ? (uint32_t)n_obs * TE_STACK_SPHERES : 1u;
     fill = FillJob{obs_lidar, 0u, lists * (uint32_t)(p.Npad >> 6), 3u, e->prev_cells, lists, (uint32_t)p.D, (uint32_t)p.Npad, (uint32_t)p.N, (uint32_t)(lidar_words_per_env / (size_t)lists)};
   } else if (obs_lidar && persist != 3) {
     const size_t quads = n_floats >> 2;
     if (quads >= 4096 && quads < (1ull << 32)) {
-      fill = FillJob{obs_lidar, (uint32_t)quads, (uint32_t)e->n_fill_waves, (quads >> 6) < (1u << 22) ? (uint32_t)e->fill_mode : 0u, nullptr, 0u, 0u, 0u, 0u, 0u};  // the SGPR block offset is 32-bit: < 4 GB
+      fill = FillJob{obs_lidar, (uint32_t)quads, (uint32_t)k.n_fill_waves, (quads >> 6) < (1u << 22) ? 1u : 0u, nullptr, 0u, 0u, 0u, 0u, 0u};  // the SGPR block offset is 32-bit: < 4 GB
       if (n_floats & 3) hipLaunchKernelGGL(fill_ones_kernel, dim3(1), dim3(64), 0, st, obs_lidar + (quads << 2), n_floats & 3);
     } else {  // tiny or huge buffers: plain fill kernel first
       hipLaunchKernelGGL(fill_ones_kernel, dim3(2048), dim3(256), 0, st, obs_lidar, n_floats);
@@ -1466,24 +1518,7 @@ static int step_impl(te_env* e, const float* actions, float* obs_lidar, size_t l
   }
   if (prof_ext) { ev_a = pev[0]; ev_b = pev[1]; }
   const int b1 = (int)fill.n_fill_waves + waves + (e->family == FAM_LEVEL4 && p.dense_min > 1 ? kMixedWaves * (p.Npad >> 6) : 0);  // + mixed-wave candidates
-  launch_by_family(e->family, [&](auto fam) {
-    constexpr int F = decltype(fam)::value;
-    auto go = [&](auto noise_c, auto fill_c) {
-      constexpr bool kNoise = decltype(noise_c)::value;
-      if (kNoise && e->k1_help) {   // small shards: every flight (and candidate) block carries a second wave that prepares the motor noise
-        const size_t lds = (size_t)p.cfg.substeps * 1024 + 16;
-        if (p.cfg.control_every_substep)
-          TE_LAUNCH((substeps_kernel<F, kNoise, decltype(fill_c)::value, true, kNoise>), dim3(b1), dim3(128), lds, p, actions, fill);
-        else
-          TE_LAUNCH((substeps_kernel<F, kNoise, decltype(fill_c)::value, false, kNoise>), dim3(b1), dim3(128), lds, p, actions, fill);
-      } else if (p.cfg.control_every_substep)
-        TE_LAUNCH((substeps_kernel<F, kNoise, decltype(fill_c)::value, true>), dim3(b1), dim3(TE_K1_BLOCK), 0, p, actions, fill);
-      else
-        TE_LAUNCH((substeps_kernel<F, kNoise, decltype(fill_c)::value, false>), dim3(b1), dim3(TE_K1_BLOCK), 0, p, actions, fill);
-    };
-    if (noise) { if (fill.lidar) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
-    else { if (fill.lidar) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
-  });
+  launch(k.substeps[fill.lidar ? 1 : 0], b1, st, ev_a, ev_b, p, actions, fill);
   if (prof && !prof_ext) { TE_HIP(hipEventRecord(pev[1], st)); TE_HIP(hipEventRecord(pev[2], st)); }
   if (prof_ext) { ev_a = pev[2]; ev_b = stack ? nullptr : pev[3]; }
   const int b2 = (p.N + kEPB - 1) / kEPB;
@@ -1491,51 +1526,17 @@ static int step_impl(te_env* e, const float* actions, float* obs_lidar, size_t l
   // output comes from stacked_kernel
   StepOut o{reward, done, info, ObsOut{stack ? nullptr : obs_lidar, obs_inertial, obs_last_action},
             ObsOut{stack ? nullptr : terminal_lidar, terminal_inertial, terminal_last_action}, e->prev_cells, stack ? 0 : persist};
-  const bool contact = p.cfg.drone_contact != 0;   // its own instantiations: the contact pass would cost every launch ~150 VGPRs
-  if (e->engage_slots == 2 && p.D > 32) TE_LAUNCH((engage_slots_multi_kernel<3, false, true>), dim3(b2), dim3(64 * e->slot_waves), e->slot_lds, p, actions, o);
-  else if (e->engage_slots == 2 && !stack) TE_LAUNCH((engage_slots_multi_kernel<2, true>), dim3(b2), dim3(64 * e->slot_waves), e->slot_lds, p, actions, o);
-  else if (e->engage_slots == 2 && e->slot_spw == 1) TE_LAUNCH((engage_slots_multi_kernel<1, false>), dim3(b2), dim3(64 * e->slot_waves), e->slot_lds, p, actions, o);
-  else if (e->engage_slots == 2 && e->slot_spw == 3) TE_LAUNCH((engage_slots_multi_kernel<3, false>), dim3(b2), dim3(64 * e->slot_waves), e->slot_lds, p, actions, o);
-  else if (e->engage_slots == 2) TE_LAUNCH((engage_slots_multi_kernel<2, false>), dim3(b2), dim3(64 * e->slot_waves), e->slot_lds, p, actions, o);
-  else if (e->engage_slots && e->family == FAM_STAGE02) TE_LAUNCH((engage_slots_stage02_kernel<kSlotWaves>), dim3(b2), dim3(64 * p.D), (size_t)slot_lds_rows(p.D, p.cfg.n_pursuers) * 256, p, actions, o);
-  else if (e->engage_slots && !contact && e->slot_wpe8) TE_LAUNCH((engage_slots_kernel<kSlotWaves, 8>), dim3(b2), dim3(64 * p.D), (size_t)slot_lds_rows(p.D, p.cfg.n_pursuers) * 256, p, actions, o);
-  else if (e->engage_slots && !contact) TE_LAUNCH((engage_slots_kernel<kSlotWaves>), dim3(b2), dim3(64 * p.D), (size_t)slot_lds_rows(p.D, p.cfg.n_pursuers) * 256, p, actions, o);
-  else if (e->engage_regs == 1 && !contact) TE_LAUNCH((engage_kernel<2, 9>), dim3(b2), dim3(64), 0, p, actions, o);
-  else if (e->engage_regs == 2 && !contact) TE_LAUNCH((engage_kernel<6, 12>), dim3(b2), dim3(64), 0, p, actions, o);
-#ifndef TE_DEBUG_STAMPS  // the stamp build leaves the contact variants out (the compiler rejects them next to the stamp stores)
-  else if (e->engage_regs == 1) TE_LAUNCH((engage_kernel<2, 9, true>), dim3(b2), dim3(64), 0, p, actions, o);
-  else if (e->engage_regs == 2) TE_LAUNCH((engage_kernel<6, 12, true>), dim3(b2), dim3(64), 0, p, actions, o);
-#endif
-  else if (e->engage_regs == 5) TE_LAUNCH((engage_kernel<7, 30>), dim3(b2), dim3(64), 0, p, actions, o);
-  else if (e->engage_regs == 3) TE_LAUNCH((engage_stage02_kernel<2, 8>), dim3(b2), dim3(64), 0, p, actions, o);
-  else if (e->engage_regs == 4) TE_LAUNCH(engage_stage01_kernel, dim3(b2), dim3(64), 0, p, actions, o);
-  else launch_by_family(e->family, [&](auto fam) {
-    if (e->k2_threads == 512) TE_LAUNCH((engage_observe_kernel<FAM_LEVEL4, 512>), dim3(b2), dim3(512), e->lds_bytes, p, actions, o);
-    else TE_LAUNCH((engage_observe_kernel<decltype(fam)::value>), dim3(b2), dim3(256), e->lds_bytes, p, actions, o);
-  });
+  launch(k.engage, b2, st, ev_a, ev_b, p, actions, o);
   if (stack) {
-    ev_a = nullptr; ev_b = nullptr;
-    // the first launch pushes this step's ring entries (all wingmen) and serves observer 0; te_step_students adds one launch per further wingman
-    if (e->stack_regs) {  // one wave per (chunk, wingman) pushes this step's ring entries, then one 5-wave workgroup per chunk and observer
-      StackParams sp{p.cfg, p.snap, p.ring, p.N, p.Npad, p.D, p.entry_words, 1, 0, n_obs, persist, e->prev_cells};
-      const unsigned push_waves = (unsigned)b2 * (unsigned)p.cfg.n_pursuers;
-      if (e->stack_regs == 18 && e->push_split) TE_LAUNCH((ring_push_kernel<18, kPushSplit>), dim3(push_waves), dim3(64 * kPushSplit), (size_t)4 * 18 * 256, sp);
-      else if (e->stack_regs == 18) TE_LAUNCH((ring_push_kernel<18, 1>), dim3(push_waves), dim3(64), 0, sp);
-      else TE_LAUNCH((ring_push_kernel<37, 1>), dim3(push_waves), dim3(64), 0, sp);
-      for (int ob = 0; ob < n_obs; ++ob) {
-        sp.push = ob == 0 ? 1 : 0; sp.observer = ob;   // the first view clears the ring of auto-reset envs when it is through
-        if (prof_ext && ob == n_obs - 1) ev_b = pev[3];
-        if (e->stack_regs == 18) TE_LAUNCH((stack_view_kernel<18>), dim3(b2), dim3(kViewThreads), e->view_lds_bytes, sp, *stack);
-        else TE_LAUNCH((stack_view_kernel<37>), dim3(b2), dim3(kViewThreads), e->view_lds_bytes, sp, *stack);
-      }
-    } else
+    ev_a = nullptr; ev_b = nullptr;   // the first launches push this step's ring entries (all wingmen) and serve observer 0; te_step_students adds one view per further wingman
+    StackParams sp{p.cfg, p.snap, p.ring, p.N, p.Npad, p.D, p.entry_words, 1, 0, n_obs, persist, e->prev_cells};
+    if (k.ring_push.fn) launch(k.ring_push, (unsigned)b2 * (unsigned)p.cfg.n_pursuers, st, ev_a, ev_b, sp);   // one wave (or kPushSplit) per (chunk, wingman)
     for (int ob = 0; ob < n_obs; ++ob) {
-      StackParams sp{p.cfg, p.snap, p.ring, p.N, p.Npad, p.D, p.entry_words, ob == 0 ? 1 : 0, ob, n_obs, 0, nullptr};
+      sp.push = ob == 0 ? 1 : 0; sp.observer = ob;   // the first view clears the ring of auto-reset envs when it is through
       if (prof_ext && ob == n_obs - 1) ev_b = pev[3];
-      TE_LAUNCH(stacked_kernel, dim3(b2), dim3(kStackThreads), e->stack_lds_bytes, sp, *stack);
+      launch(k.stack_view, b2, st, ev_a, ev_b, sp, *stack);
     }
   }
-#undef TE_LAUNCH
   e->last_stacked = persist ? obs_lidar : nullptr; e->last_n_obs = n_obs;
   if (prof) { if (!prof_ext) TE_HIP(hipEventRecord(pev[3], st)); e->prof_used += 4; }
   TE_HIP(hipGetLastError());
@@ -1624,7 +1625,7 @@ __attribute__((visibility("default"))) int te_set_persistent_obs(te_env* e, int3
   if (!e) return fail("te_set_persistent_obs: null env");
   DeviceGuard guard(e->device);
   e->last_stacked = nullptr;
-  e->persist_on = on != 0 && (e->p.ring ? e->stack_regs != 0 : e->engage_regs != 0);   // the register kernels record what they patch; the LDS fallbacks stay dense
+  e->persist_on = on != 0 && e->k.records_cells;   // the register kernels record what they patch; the LDS fallbacks stay dense
   if (e->persist_on && !e->prev_cells) {
     const int observers = !e->p.ring ? 1 : all_scripted(e->p.cfg) ? e->p.cfg.n_pursuers : 1;   // te_step_students serves every wingman
     const size_t bytes = (size_t)observers * (e->p.ring ? TE_STACK_SPHERES : 1) * (size_t)e->p.D * (size_t)e->p.Npad * sizeof(uint16_t);
@@ -1710,14 +1711,12 @@ __attribute__((visibility("default"))) int te_observe_stacked(te_env* e, float* 
   if (p.D > kMaxD) {  // Level5FusionTask (36 drones): observe_kernel stages at most 32 slots; the two rows need none of them
     if (obs_inertial || obs_last_action) hipLaunchKernelGGL(agent_rows_kernel, dim3((p.N + 255) / 256), dim3(256), 0, st, p, obs_inertial, obs_last_action);
   } else {
-    hipLaunchKernelGGL(observe_kernel, dim3(blocks), dim3(256), e->lds_bytes, st, p, ObsOut{nullptr, obs_inertial, obs_last_action});
+    hipLaunchKernelGGL(observe_kernel, dim3(blocks), dim3(256), e->k.observe_lds, st, p, ObsOut{nullptr, obs_inertial, obs_last_action});
   }
-  const int persist = (e->persist_on && e->stack_regs && e->prev_observers >= 1) ? 2 : 0;   // dense fill above; the cells are recorded for the next step
+  const int persist = (e->persist_on && e->prev_observers >= 1) ? 2 : 0;   // dense fill above; the cells are recorded for the next step
   StackParams sp{p.cfg, p.snap, p.ring, p.N, p.Npad, p.D, p.entry_words, 0, 0, 1, persist, e->prev_cells};
   e->last_stacked = persist ? obs_stacked : nullptr; e->last_n_obs = 1;
-  if (e->stack_regs == 18) hipLaunchKernelGGL((stack_view_kernel<18>), dim3(blocks), dim3(kViewThreads), e->view_lds_bytes, st, sp, StackOut{obs_stacked, obs_mask, nullptr, nullptr});
-  else if (e->stack_regs == 37) hipLaunchKernelGGL((stack_view_kernel<37>), dim3(blocks), dim3(kViewThreads), e->view_lds_bytes, st, sp, StackOut{obs_stacked, obs_mask, nullptr, nullptr});
-  else hipLaunchKernelGGL(stacked_kernel, dim3(blocks), dim3(kStackThreads), e->stack_lds_bytes, st, sp, StackOut{obs_stacked, obs_mask, nullptr, nullptr});
+  launch(e->k.stack_view, blocks, st, nullptr, nullptr, sp, StackOut{obs_stacked, obs_mask, nullptr, nullptr});
   TE_HIP(hipGetLastError());
   return 0;
 }

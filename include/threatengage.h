@@ -418,6 +418,13 @@ int te_set_state(te_env* env, const void* src_device, size_t words, void* stream
 /* Algorithmic HBM bytes one te_step moves per environment (SURVEY.md 8(d) formula). */
 int te_algorithmic_bytes_per_env_step(const te_config* cfg, size_t* out_bytes);
 
+/* The kernels te_create would choose for `cfg` under the current environment knobs, one "role=kernel" line each:
+ * substeps, substeps_nofill (the sub-step kernel with and without the background's fill waves), engage, and for cfg.stacked_obs
+ * ring_push (absent when stacked_kernel serves the observation) and stack_view.  Kernel names as rocprofv3 prints them, without
+ * the namespace and the signature.  Needs no device; an invalid config fails with te_create's message.  (On a device that refuses
+ * a multi-slot engage kernel more than 64 KB of LDS, te_create falls back to the form without it.)  out holds out_bytes bytes. */
+int te_kernel_plan(const te_config* cfg, char* out, size_t out_bytes);
+
 /* Kernel timing with HIP events on the stream te_step launches on.  After te_profile_begin the next
  * `max_steps` te_step calls launch their kernels with start / stop events (hipExtLaunchKernelGGL: the
  * dispatch's own begin / end timestamps, the quantity rocprofv3 --kernel-trace reports; TE_PROF=markers

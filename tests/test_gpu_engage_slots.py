@@ -14,12 +14,15 @@ def _pair(monkeypatch, task, n, **over):
     if not torch.cuda.is_available():
         pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
     from dronechase_amd import default_config
+    from dronechase_amd._lib import kernel_plan
     from dronechase_amd.batched_env import BatchedEnv
-    envs = []
+    envs, engage = [], []
     for mode in ("slots", "regs"):
         monkeypatch.setenv("TE_ENGAGE", mode)
+        engage.append(kernel_plan(default_config(task, n_envs=n, **over))["engage"])
         envs.append(BatchedEnv(default_config(task, n_envs=n, **over), "cuda:0"))
     monkeypatch.delenv("TE_ENGAGE")
+    assert engage[0] != engage[1], f"TE_ENGAGE=slots and regs both run {engage[0]}"
     return envs
 
 
@@ -209,12 +212,15 @@ def _pair_var(monkeypatch, var, values, task, n, **over):
     if not torch.cuda.is_available():
         pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
     from dronechase_amd import default_config
+    from dronechase_amd._lib import kernel_plan
     from dronechase_amd.batched_env import BatchedEnv
-    envs = []
+    envs, plans = [], []
     for v in values:
         monkeypatch.setenv(var, v)
+        plans.append(kernel_plan(default_config(task, n_envs=n, **over)))
         envs.append(BatchedEnv(default_config(task, n_envs=n, **over), "cuda:0"))
     monkeypatch.delenv(var)
+    assert plans[0] != plans[1], f"{var}={values[0]} and {values[1]} run the same kernels: {plans[0]}"
     return envs
 
 

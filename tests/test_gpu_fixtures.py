@@ -462,11 +462,14 @@ def test_transform_features_fixture_through_the_c_abi():
     from oracle import te_oracle as O          # stack_draws only: which neighbour / age / shuffle env i draws (shared Philox stream)
     from tests import _transform_fixture as TF
     fx = TF.load()
+    from dronechase_amd._lib import kernel_plan
     cfg = default_config("level5_c1", n_envs=256, seed=11)
+    views = []
     for mode in ("regs", "lds"):
         if mode == "lds":
             os.environ["TE_STACKED"] = "lds"
         try:
+            views.append(kernel_plan(cfg)["stack_view"])
             g = _gpu(cfg)
         finally:
             os.environ.pop("TE_STACKED", None)
@@ -479,6 +482,7 @@ def test_transform_features_fixture_through_the_c_abi():
         info = TF.check(cfg, fx, stacked.cpu().numpy(), mask.cpu().numpy(), episodes, lambda e, ep: O.stack_draws(cfg, e, ep, TF.STEP, 0b11))
         assert info["hit_cells_compared"] > 500, (mode, info)
         g.close()
+    assert views == ["stack_view_kernel<18>", "stacked_kernel"], views
 
 
 def test_spawn_sampler_fixture_through_the_c_abi(golden):

@@ -217,9 +217,12 @@ def test_heterogeneous_chunk_ring_matches_lds_fallback_and_oracle(task, monkeypa
     cfg = default_config(task, n_envs=N, motor_noise=0, seed=21)
     P, D = int(cfg.n_pursuers), int(cfg.n_drones)
     students = task == "level5_dumb"
+    from dronechase_amd._lib import kernel_plan
     g = BatchedEnv(cfg, "cuda:0")
+    view = kernel_plan(cfg)["stack_view"]
     monkeypatch.setenv("TE_STACKED", "lds")
     h = BatchedEnv(cfg, "cuda:0")
+    assert kernel_plan(cfg)["stack_view"] == "stacked_kernel" != view
     monkeypatch.delenv("TE_STACKED")
     o = O.OracleEnv(cfg, "f32", threads=4)
     g.reset()

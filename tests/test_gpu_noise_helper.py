@@ -12,12 +12,15 @@ def _pair(monkeypatch, task, n, **over):
     if not torch.cuda.is_available():
         pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
     from dronechase_amd import default_config
+    from dronechase_amd._lib import kernel_plan
     from dronechase_amd.batched_env import BatchedEnv
-    envs = []
+    envs, substeps = [], []
     for mode in ("1", "0"):
         monkeypatch.setenv("TE_K1_HELP", mode)
+        substeps.append(kernel_plan(default_config(task, n_envs=n, motor_noise=1, **over))["substeps"])
         envs.append(BatchedEnv(default_config(task, n_envs=n, motor_noise=1, **over), "cuda:0"))
     monkeypatch.delenv("TE_K1_HELP")
+    assert substeps[0] != substeps[1], f"TE_K1_HELP=1 and 0 both run {substeps[0]}"
     return envs
 
 
