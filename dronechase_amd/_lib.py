@@ -18,11 +18,17 @@ EXPORTS = (
     "te_state_words", "te_get_state", "te_set_state", "te_algorithmic_bytes_per_env_step", "te_profile_begin",
     "te_profile_end", "te_debug_stamps", "te_abi_version", "te_last_error", "te_step_stacked", "te_observe_stacked", "te_observe_ally", "te_set_ally_actions", "te_wingman_info", "te_calculate_rounds", "te_observe_wingman", "te_set_wingman_actions", "te_drive_wingman", "te_quad_preset", "te_step_students", "te_set_persistent_obs",
     "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad", "te_kernel_plan",
+    "te_monitor_bytes", "te_monitor_layout", "te_monitor_init", "te_monitor_step", "te_monitor_stats",
 )
 
 
 class TEError(RuntimeError):
     pass
+
+
+class MonitorOffsets(C.Structure):
+    """te_monitor_offsets: byte offsets of the arrays inside an episode-monitor buffer (include/threatengage.h)."""
+    _fields_ = [(n, C.c_size_t) for n in ("bytes", "n_rows", "rows", "ret", "len", "episodes", "last_ret", "last_len", "rec_info", "rec_ret", "rec_len")]
 
 
 def load() -> C.CDLL:
@@ -74,6 +80,12 @@ def load() -> C.CDLL:
     L.te_policy_grad_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
     f32 = C.c_float
     L.te_policy_ppo_grad.argtypes = [vp, i32, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]
+    mon = [vp, C.c_size_t, i32, i32]
+    L.te_monitor_bytes.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
+    L.te_monitor_layout.argtypes = [i32, i32, C.POINTER(MonitorOffsets)]
+    L.te_monitor_init.argtypes = mon + [vp]
+    L.te_monitor_step.argtypes = mon + [vp, vp, vp, vp]
+    L.te_monitor_stats.argtypes = mon + [vp, i32, vp]
     if L.te_abi_version() != K.TE_ABI_VERSION:
         raise RuntimeError("libthreatengage.so ABI version differs from dronechase_amd.config")
     _LIB = L

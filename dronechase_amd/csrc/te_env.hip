@@ -42,6 +42,7 @@
 #include "te_engage_slots.hpp"
 #include "te_policy.hpp"
 #include "te_policy_grad.hpp"
+#include "te_monitor.hpp"
 
 namespace te {
 
@@ -2029,6 +2030,67 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* param
   hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- episode monitor (te_monitor.hpp): every check is on the host, before any launch
+static int monitor_check(const char* who, const void* mon, size_t bytes, int32_t n_envs, int32_t n_records) {
+  const std::string w(who);
+  if (n_envs <= 0) return fail(w + ": n_envs must be positive");
+  if (n_records < 0) return fail(w + ": n_records must be >= 0");
+  if (!mon) return fail(w + ": null monitor buffer");
+  if ((uintptr_t)mon & 15) return fail(w + ": the monitor buffer must be 16-byte aligned");
+  const size_t need = monitor_offsets(n_envs, n_records).bytes;
+  if (bytes < need)
+    return fail(w + ": monitor buffer too small (" + std::to_string(bytes) + " bytes, te_monitor_bytes says " + std::to_string(need) + ")");
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_monitor_layout(int32_t n_envs, int32_t n_records, te_monitor_offsets* out) {
+  if (!out) return fail("te_monitor_layout: null argument");
+  if (n_envs <= 0) return fail("te_monitor_layout: n_envs must be positive");
+  if (n_records < 0) return fail("te_monitor_layout: n_records must be >= 0");
+  *out = monitor_offsets(n_envs, n_records);
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_monitor_bytes(int32_t n_envs, int32_t n_records, size_t* out_bytes) {
+  if (!out_bytes) return fail("te_monitor_bytes: null argument");
+  te_monitor_offsets o;
+  if (n_envs <= 0) return fail("te_monitor_bytes: n_envs must be positive");
+  if (n_records < 0) return fail("te_monitor_bytes: n_records must be >= 0");
+  o = monitor_offsets(n_envs, n_records);
+  *out_bytes = o.bytes;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_monitor_init(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, void* stream) {
+  if (monitor_check("te_monitor_init", mon, bytes, n_envs, n_records)) return 1;
+  TE_HIP(hipMemsetAsync(mon, 0, monitor_offsets(n_envs, n_records).bytes, (hipStream_t)stream));
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_monitor_step(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, const float* reward,
+                                                           const uint8_t* done, const int32_t* info, void* stream) {
+  if (monitor_check("te_monitor_step", mon, bytes, n_envs, n_records)) return 1;
+  if (!reward || !done || !info) return fail("te_monitor_step: null argument");
+  if ((uintptr_t)reward & 3) return fail("te_monitor_step: reward must be 4-byte aligned");
+  if ((uintptr_t)info & 15) return fail("te_monitor_step: info must be 16-byte aligned");
+  const dim3 grid((unsigned)((n_envs + kMonThreads - 1) / kMonThreads));
+  hipLaunchKernelGGL(monitor_step_kernel, grid, dim3(kMonThreads), 0, (hipStream_t)stream, monitor_view(mon, n_envs, n_records), reward, done,
+                     reinterpret_cast<const int4*>(info));
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_monitor_stats(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, te_monitor_summary* out,
+                                                            int32_t reset_window, void* stream) {
+  if (monitor_check("te_monitor_stats", mon, bytes, n_envs, n_records)) return 1;
+  if (!out) return fail("te_monitor_stats: null argument");
+  if ((uintptr_t)out & 7) return fail("te_monitor_stats: out must be 8-byte aligned");
+  hipLaunchKernelGGL(monitor_stats_kernel, dim3(1), dim3(kMonThreads), 0, (hipStream_t)stream, monitor_view(mon, n_envs, n_records), out,
+                     (int)reset_window);
   TE_HIP(hipGetLastError());
   return 0;
 }

@@ -1,0 +1,267 @@
+"""Episode monitor and SB3-style policy evaluation, on the device.
+
+What SB3 does in Python on the host around a VecEnv, done next to the step instead:
+  * VecMonitor.step_wait: the running return and length of every env's episode, and (r, l) of the episode an env just finished
+    (`infos[i]["episode"]`, ThreatEngageVecEnv(episode_monitor=True));
+  * the logger's ep_rew_mean / ep_len_mean over the episodes of a window (PPOConfig.episode_stats), plus the means of the info row
+    an episode ended with (agent_kills, allies_kills, deads, current_wave: what the exp05 curriculum decides on);
+  * evaluate_policy: a fixed number of episodes with per-env quotas (evaluate_policy below), which is what the reference's
+    ReinforcementLearningPipeline.evaluate ranks hyper-parameters by (src/core/rl_framework/utils/pipeline.py:374-414).
+
+On a GPU the bookkeeping is te_monitor_step (one launch per step, no host synchronisation, capturable in a HIP graph) on one
+caller-owned buffer; the host reads 80 bytes per stats() and 4 bytes per recorded().  On a CPU device the same semantics run in
+numpy: that serves stub backends and lets the API, the quotas and evaluate_policy be tested without a GPU.  It is not a fallback
+for a missing kernel: a CUDA device always takes the HIP path."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+
+INFO_MEAN_KEYS = ("ep_agent_kills_mean", "ep_allies_kills_mean", "ep_deads_mean", "ep_wave_mean")   # info[0..3], vec_env.INFO_KEYS
+
+_SUMMARY = np.dtype([("count", "<i8"), ("sum_len", "<i8"), ("sum_info", "<i8", (4,)), ("sum_ret", "<f8"), ("sum_ret2", "<f8"),
+                     ("min_ret", "<f4"), ("max_ret", "<f4"), ("recorded", "<i4"), ("reserved", "<i4")])   # te_monitor_summary
+assert _SUMMARY.itemsize == 80
+
+
+def episode_quotas(n_envs: int, n_records: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(quota [N], offset [N]) of evaluate_policy's episode counts: quota_e = (n_records + e) // N in closed form, and the exclusive
+    prefix sum of the quotas: env e's k-th episode (k < quota_e) goes to record slot offset_e + k."""
+    if n_envs <= 0 or n_records < 0:
+        raise ValueError("episode_quotas: n_envs must be positive and n_records >= 0")
+    e = np.arange(n_envs, dtype=np.int64)
+    q, r = divmod(int(n_records), int(n_envs))
+    return q + (e >= n_envs - r), e * q + np.maximum(0, e - (n_envs - r))
+
+
+def _summary_to_stats(s) -> Dict[str, float]:
+    """te_monitor_summary -> the logged keys.  With no episode in the window only `count` is there (SB3 omits ep_rew_mean then)."""
+    n = int(s["count"])
+    out: Dict[str, float] = {"count": n}
+    if n == 0:
+        return out
+    mean = float(s["sum_ret"]) / n
+    out["ep_rew_mean"] = mean
+    out["ep_rew_std"] = float(np.sqrt(max(0.0, float(s["sum_ret2"]) / n - mean * mean)))   # ddof 0
+    out["ep_rew_min"], out["ep_rew_max"] = float(s["min_ret"]), float(s["max_ret"])
+    out["ep_len_mean"] = int(s["sum_len"]) / n
+    for k, v in zip(INFO_MEAN_KEYS, s["sum_info"]):
+        out[k] = int(v) / n
+    return out
+
+
+class EpisodeMonitor:
+    """Episode returns, lengths and final info rows of N environments, fed once per env step.
+
+    step(reward [N] f32, done [N] u8 / bool, info [N, 4] i32) after every env step; stats() = the episodes that finished since the
+    last stats(reset=True); with n_records > 0 the first quota_e episodes of every env are also kept one by one (records())."""
+
+    def __init__(self, n_envs: int, device, n_records: int = 0):
+        self.N, self.R = int(n_envs), int(n_records)
+        if self.N <= 0 or self.R < 0:
+            raise ValueError("EpisodeMonitor: n_envs must be positive and n_records >= 0")
+        self.device = torch.device(device)
+        self.on_gpu = self.device.type == "cuda"
+        if self.on_gpu:
+            self.L = _lib.load()
+            o = _lib.MonitorOffsets()
+            _lib.check(self.L.te_monitor_layout(self.N, self.R, C.byref(o)), "te_monitor_layout")
+            self._o = o
+            self.buf = torch.empty(int(o.bytes), dtype=torch.uint8, device=self.device)
+            self.device = self.buf.device        # "cuda" -> "cuda:N": the device the callers' tensors report
+            self._summary = torch.empty(_SUMMARY.itemsize, dtype=torch.uint8, device=self.device)
+            N, R = self.N, self.R
+            self._recorded = self.buf[0:4].view(torch.int32)
+            self.last_ret = self.buf[o.last_ret:o.last_ret + 4 * N].view(torch.float32)
+            self.last_len = self.buf[o.last_len:o.last_len + 4 * N].view(torch.int32)
+            self._rec = (self.buf[o.rec_ret:o.rec_ret + 4 * R].view(torch.float32), self.buf[o.rec_len:o.rec_len + 4 * R].view(torch.int32),
+                         self.buf[o.rec_info:o.rec_info + 16 * R].view(torch.int32).view(R, 4))
+        else:
+            self.quota, self.offset = episode_quotas(self.N, self.R)
+        self.reset()
+
+    # ------------------------------------------------------------------ plumbing
+    def _args(self):
+        return self.buf.data_ptr(), self.buf.numel(), self.N, self.R
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self) -> None:
+        """Forget everything: partial episodes, the window, the records."""
+        if self.on_gpu:
+            with torch.cuda.device(self.device):
+                _lib.check(self.L.te_monitor_init(*self._args(), self._stream()), "te_monitor_init")
+            return
+        N, R = self.N, self.R
+        self._s = dict(ret=np.zeros(N, np.float32), len=np.zeros(N, np.int32), episodes=np.zeros(N, np.int32),
+                       last_ret=np.zeros(N, np.float32), last_len=np.zeros(N, np.int32), rec_ret=np.zeros(R, np.float32),
+                       rec_len=np.zeros(R, np.int32), rec_info=np.zeros((R, 4), np.int32), window=np.zeros((), _SUMMARY))
+        self.last_ret, self.last_len = torch.from_numpy(self._s["last_ret"]), torch.from_numpy(self._s["last_len"])
+
+    # ------------------------------------------------------------------ API
+    def step(self, reward: torch.Tensor, done: torch.Tensor, info: torch.Tensor) -> None:
+        N = self.N
+        if done.dtype == torch.bool:
+            done = done.view(torch.uint8)
+        for name, t, shape, dt in (("reward", reward, (N,), torch.float32), ("done", done, (N,), torch.uint8), ("info", info, (N, 4), torch.int32)):
+            if tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"EpisodeMonitor.step: {name} must be a contiguous {dt} {shape} tensor on {self.device}")
+        if self.on_gpu:
+            with torch.cuda.device(self.device):
+                _lib.check(self.L.te_monitor_step(*self._args(), reward.data_ptr(), done.data_ptr(), info.data_ptr(), self._stream()), "te_monitor_step")
+            return
+        s, w = self._s, self._s["window"]
+        s["ret"] += reward.detach().numpy()          # float32 + float32: one rounding per step
+        s["len"] += 1
+        inf = info.detach().numpy()
+        for e in np.flatnonzero(done.detach().numpy()):
+            r, l, k = s["ret"][e], int(s["len"][e]), int(s["episodes"][e])
+            first = int(w["count"]) == 0
+            w["count"] += 1; w["sum_len"] += l; w["sum_info"] += inf[e]
+            w["sum_ret"] += float(r); w["sum_ret2"] += float(r) * float(r)
+            w["min_ret"] = r if first else min(float(w["min_ret"]), float(r))
+            w["max_ret"] = r if first else max(float(w["max_ret"]), float(r))
+            if k < self.quota[e]:
+                at = int(self.offset[e]) + k
+                s["rec_ret"][at], s["rec_len"][at], s["rec_info"][at] = r, l, inf[e]
+                w["recorded"] += 1
+            s["episodes"][e] = k + 1
+            s["last_ret"][e], s["last_len"][e] = r, l
+            s["ret"][e], s["len"][e] = 0.0, 0
+
+    def summary(self, reset: bool = True) -> np.ndarray:
+        """The window's raw te_monitor_summary (a numpy record: count, sum_len, sum_info[4], sum_ret, sum_ret2, min_ret, max_ret,
+        recorded).  One 80-byte host read; reset=True starts a new window (partial episodes carry over)."""
+        if self.on_gpu:
+            with torch.cuda.device(self.device):
+                _lib.check(self.L.te_monitor_stats(*self._args(), self._summary.data_ptr(), 1 if reset else 0, self._stream()), "te_monitor_stats")
+            return self._summary.cpu().numpy().view(_SUMMARY)[0]
+        out = self._s["window"].copy()
+        if reset:
+            rec = int(out["recorded"])
+            self._s["window"] = np.zeros((), _SUMMARY)
+            self._s["window"]["recorded"] = rec      # `recorded` belongs to the records, not to the window
+        return out
+
+    def stats(self, reset: bool = True) -> Dict[str, float]:
+        """{"count", "ep_rew_mean", "ep_rew_std" (ddof 0), "ep_rew_min", "ep_rew_max", "ep_len_mean", "ep_agent_kills_mean",
+        "ep_allies_kills_mean", "ep_deads_mean", "ep_wave_mean"} of the episodes that finished in the window; everything but
+        "count" is absent (not NaN) when no episode did."""
+        return _summary_to_stats(self.summary(reset))
+
+    def recorded(self) -> int:
+        """How many record slots are written (one 4-byte host read); n_records when every env has met its quota."""
+        return int(self._recorded.item()) if self.on_gpu else int(self._s["window"]["recorded"])
+
+    def records(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(returns [R] f32, lengths [R] i32, info [R, 4] i32), env-major, then by episode ordinal (episode_quotas gives every env's
+        slots).  Only the slots recorded so far are valid: an unwritten slot has length 0."""
+        if self.on_gpu:
+            return tuple(t.cpu().numpy() for t in self._rec)
+        return self._s["rec_ret"].copy(), self._s["rec_len"].copy(), self._s["rec_info"].copy()
+
+    def state(self):
+        """A copy of the whole monitor (a plain device copy of the buffer); load_state() restores it."""
+        if self.on_gpu:
+            return self.buf.clone()
+        return {k: v.copy() for k, v in self._s.items()}
+
+    def load_state(self, state) -> None:
+        if self.on_gpu:
+            self.buf.copy_(state)
+            return
+        for k, v in state.items():
+            self._s[k][...] = v
+
+
+# ---------------------------------------------------------------------- evaluation
+DEFAULT_MAX_STEPS = 1_000_000   # see evaluate_policy
+
+
+def _actor(policy, deterministic: bool):
+    """obs dict -> clamped actions [N, 4], for every kind of policy evaluate_policy takes."""
+    from .ppo import PPO, FusedPolicy, PolicyDriver
+
+    if isinstance(policy, PPO):
+        policy = policy.fused if policy.fused is not None else policy.policy
+    if isinstance(policy, FusedPolicy):
+        fused = policy
+        fused.refresh()
+
+        def act(obs):
+            # te_policy_act's own clamp: eps = 0 gives action_env = clamp(mu); a draw gives the clamped sample
+            n = obs["lidar"].shape[0]
+            eps = torch.zeros((n, 4), device=fused.device) if deterministic else torch.randn((n, 4), device=fused.device)
+            return fused.act({k: v.contiguous() for k, v in obs.items()}, eps)[3]
+        return act
+    if isinstance(policy, torch.nn.Module):
+        policy = PolicyDriver(policy, fused=False)
+    if not hasattr(policy, "predict"):
+        raise TypeError("evaluate_policy: policy must be a LidarInertialActionPolicy, a FusedPolicy, a PolicyDriver, a PPO or an object with "
+                        "predict(obs, deterministic=...)")
+    return lambda obs: policy.predict(obs, deterministic=deterministic)[0]
+
+
+@torch.no_grad()
+def evaluate_policy(policy, env, n_eval_episodes: int = 100, deterministic: bool = True, wingman_policy=None, poll_every: int = 16,
+                    max_steps: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """SB3's evaluate_policy(return_episode_rewards=True) with everything on the env's device: (episode_rewards [n] f32,
+    episode_lengths [n] i32), exactly n_eval_episodes entries, env-major.
+
+    `env` is a BatchedEnv or a ThreatEngageVecEnv; it is reset first.  Of a ThreatEngageVecEnv the .backend is reset and stepped
+    directly, past the wrapper's own bookkeeping (a pending step_async, reset_infos, its episode_monitor): call its reset() before
+    using it as a VecEnv again.  Env e contributes its FIRST
+    (n_eval_episodes + e) // N episodes, as in SB3, so envs with short episodes are not over-represented.  The rewards are the
+    env's raw rewards (PPOConfig.reward_scale does not apply).  `policy`: a LidarInertialActionPolicy, a FusedPolicy, a
+    PolicyDriver, or a PPO (its learner).  deterministic=True steps with mu clamped to [-1, 1]^3 x [0, 1] (through te_policy_act
+    when the policy is fused), False with a clamped sample.  Caller-driven pursuers (exp05's ally, the evaluation task's driver
+    mask) are flown by `wingman_policy` (a module or a FusedPolicy; default: a PPO's own wingman) with one drive_wingman call per
+    pursuer before every step, as PPO's rollout does.
+    The host reads 4 bytes (the number of recorded episodes) every `poll_every` steps and never per step; steps taken after
+    the last quota is met change nothing.  max_steps bounds the loop: if it is reached with fewer than n_eval_episodes recorded,
+    RuntimeError says how many were.  Default 1 000 000 steps, far more than any task's episodes need (a stage03 episode is at most a
+    few thousand steps): the cap exists to turn an env that never finishes an episode into an error instead of a hang."""
+    from .ppo import PPO, FusedPolicy, caller_driven_pursuers
+
+    backend = getattr(env, "backend", env)
+    n = int(n_eval_episodes)
+    if n <= 0 or int(poll_every) <= 0:
+        raise ValueError("evaluate_policy: n_eval_episodes and poll_every must be positive")
+    max_steps = DEFAULT_MAX_STEPS if max_steps is None else int(max_steps)
+    cfg = getattr(backend, "cfg", None)
+    if cfg is not None and bool(getattr(cfg, "stacked_obs", 0)):
+        raise ValueError("evaluate_policy: the stacked (level5) observation has no policy in this package")
+    wingmen = caller_driven_pursuers(cfg)
+    if wingmen:
+        if wingman_policy is None and isinstance(policy, PPO):
+            wingman_policy = policy.wingman
+        if wingman_policy is None:
+            raise ValueError("evaluate_policy: this environment has caller-driven pursuers (exp05's ally, the evaluation driver mask): pass wingman_policy")
+        wingman = wingman_policy if isinstance(wingman_policy, FusedPolicy) else FusedPolicy(wingman_policy)
+        wingman.refresh()
+    act = _actor(policy, deterministic)
+    obs = backend.reset()
+    if obs is None:
+        raise ValueError("evaluate_policy: this environment's reset returns no observation")
+    monitor = EpisodeMonitor(backend.N, backend.device, n_records=n)
+    keys = ("lidar", "inertial_data", "last_action")
+    steps, recorded = 0, 0
+    while recorded < n:
+        if steps >= max_steps:
+            raise RuntimeError(f"evaluate_policy: {recorded} of {n} episodes recorded after max_steps = {max_steps} steps")
+        a = act(dict(zip(keys, obs[:3]))).contiguous()
+        for w in wingmen:
+            backend.drive_wingman(w, wingman)
+        *obs, reward, done, info = backend.step(a, terminal=False)
+        monitor.step(reward, done, info)
+        steps += 1
+        if steps % poll_every == 0 or steps >= max_steps:
+            recorded = monitor.recorded()
+    returns, lengths, _ = monitor.records()
+    return returns, lengths

@@ -1,10 +1,14 @@
 """Mirror of ReinforcementLearningPipeline.create_vectorized_environment
 (src/core/rl_framework/utils/pipeline.py:31-61): same arguments and kwarg white-list, but returns ONE
-batched GPU VecEnv instead of VecMonitor(SubprocVecEnv([env]*n))."""
+batched GPU VecEnv instead of VecMonitor(SubprocVecEnv([env]*n)); and of its evaluate (pipeline.py:374-414) over the
+on-device evaluate_policy of monitor.py.  `episode_monitor=True` (forwarded to ThreatEngageVecEnv) is VecMonitor's
+infos[i]["episode"] without stable-baselines3."""
 from __future__ import annotations
 
 import os
 from typing import Optional
+
+import numpy as np
 
 from .envs import ENV_TASKS
 from .vec_env import ThreatEngageVecEnv
@@ -31,3 +35,13 @@ class ReinforcementLearningPipeline:
             except Exception:
                 pass
         return venv
+
+    @staticmethod
+    def evaluate(model, env, n_eval_episodes: int = 100, deterministic: bool = True):
+        """(avg_reward, std_dev, n_eval_episodes, episode_rewards) over exactly n_eval_episodes episodes of `env` (reset first) flown
+        by `model` (anything monitor.evaluate_policy takes): the mean and np.std (ddof 0) of the raw episode returns."""
+        from .monitor import evaluate_policy
+
+        episode_rewards, _ = evaluate_policy(model, env, n_eval_episodes=n_eval_episodes, deterministic=deterministic)
+        avg_reward, std_dev = float(np.mean(episode_rewards, dtype=np.float64)), float(np.std(episode_rewards, dtype=np.float64))
+        return avg_reward, std_dev, n_eval_episodes, episode_rewards

@@ -19,6 +19,8 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
     the PyTorch forward + autograd, reading the rollout rows through the minibatch index (no gather of the observations);
   * PPOConfig.wingman_driver / PPO(wingman_policy=...): exp05's ally (and the evaluation task's "nn" drivers) flown by a frozen
     policy inside the rollout, one te_drive_wingman call per caller-driven pursuer before every te_step;
+  * PPOConfig.episode_stats / PPO.evaluate: episode returns, lengths and final info rows accumulated on the device (monitor.py,
+    te_monitor_step), and SB3's evaluate_policy over a separate evaluation env;
   * multi-GPU: one process per GPU, each with its own env shard; gradients are averaged with
     torch.distributed all_reduce (RCCL) — the only collective of the whole system, once per minibatch.
 """
@@ -270,6 +272,12 @@ class PPOConfig:
     # call per pursuer (observe, deterministic forward, clamp, drive) runs before every te_step, in both collect paths
     wingman_driver: str = "none"
     wingman_sync_every: int = 1
+    # collect() also returns the statistics of the episodes that FINISHED during it (SB3's ep_rew_mean / ep_len_mean, plus the means of
+    # the info row they ended with): an EpisodeMonitor (monitor.py, te_monitor_step) is fed the raw reward, done and info of every rollout
+    # step on the device, one extra launch per step and one 80-byte host read per collect().  An episode still running at the end of a
+    # collect() carries over to the next.  Keys other than "ep_count" are absent when no episode finished.  With several GPUs the
+    # statistics are rank-local (each rank's own env shard; no collective).  Off by default: collect()'s dict is unchanged
+    episode_stats: bool = False
 
 
 class RolloutBuffer:
@@ -390,6 +398,10 @@ class PPO:
         self._grad_stats = torch.zeros(4, device=self.device)
         self.direct = env.N % 2 == 0   # slot t of the LIDAR buffer starts on a 16-byte boundary (4 056 bytes per env)
         self._obs = None               # set by the first collect(): te_observe of the reset state
+        self.monitor = None
+        if self.cfg.episode_stats:
+            from .monitor import EpisodeMonitor
+            self.monitor = EpisodeMonitor(env.N, self.device, n_records=0)
         self.num_timesteps = 0
 
     def sync_wingmen(self) -> None:
@@ -470,11 +482,13 @@ class PPO:
             b.actions[t].copy_(self._g["a"]); b.logp[t].copy_(self._g["logp"]); b.values[t].copy_(self._g["v"])
             torch.mul(self._g["reward"], c.reward_scale, out=b.rewards[t]); b.dones[t].copy_(self._g["done"])
             ep_rew += self._g["reward"].mean(); ep_n += self._g["done"].sum().long()
+            if self.monitor is not None:   # after replay(), outside the graph: the warm-up and capture steps never reach the monitor
+                self.monitor.step(self.env.reward, self.env.done, self.env.info)
         self._obs = self._g_obs
         _, last_v = (self.fused or self.policy)(self._obs)
         b.finish(last_v, c.gamma, c.gae_lambda)
         self.num_timesteps += c.n_steps * self.env.N
-        return {"mean_step_reward": float(ep_rew) / c.n_steps, "episodes_finished": int(ep_n)}
+        return {"mean_step_reward": float(ep_rew) / c.n_steps, "episodes_finished": int(ep_n), **self._episode_stats()}
 
     @torch.no_grad()
     def collect(self) -> Dict[str, float]:
@@ -515,12 +529,31 @@ class PPO:
             b.rewards[t] = reward * c.reward_scale
             b.dones[t] = done.float()
             ep_rew += reward.mean(); ep_n += done.sum()   # stays on the device: one sync per rollout, not per step
+            if self.monitor is not None:
+                self.monitor.step(reward, done, _info)
         self._obs = {"lidar": lidar, "inertial_data": inertial, "last_action": last_action}
         _, last_v = (self.fused or self.policy)(self._obs)
         ep_rew, ep_n = float(ep_rew), int(ep_n)
         b.finish(last_v, c.gamma, c.gae_lambda)
         self.num_timesteps += c.n_steps * self.env.N
-        return {"mean_step_reward": ep_rew / c.n_steps, "episodes_finished": ep_n}
+        return {"mean_step_reward": ep_rew / c.n_steps, "episodes_finished": ep_n, **self._episode_stats()}
+
+    def _episode_stats(self) -> Dict[str, float]:
+        """PPOConfig.episode_stats: the monitor's window (the episodes that finished during this collect()) as log keys, and a new window."""
+        if self.monitor is None:
+            return {}
+        stats = self.monitor.stats(reset=True)
+        stats["ep_count"] = stats.pop("count")
+        return stats
+
+    def evaluate(self, env, n_eval_episodes: int = 100, deterministic: bool = True, **kwargs):
+        """SB3 EvalCallback's evaluate_policy of the learner on a SEPARATE evaluation env (monitor.evaluate_policy: it is reset and
+        stepped; the training env is never touched): (episode_rewards, episode_lengths), raw rewards."""
+        from .monitor import evaluate_policy
+
+        if getattr(env, "backend", env) is self.env:
+            raise ValueError("PPO.evaluate takes a separate evaluation env: evaluating on the training env would reset it mid-rollout")
+        return evaluate_policy(self, env, n_eval_episodes=n_eval_episodes, deterministic=deterministic, **kwargs)
 
     def update(self) -> Dict[str, float]:
         b, c = self.buf, self.cfg

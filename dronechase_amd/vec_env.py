@@ -6,6 +6,7 @@ SB3 is not required: the class is duck-typed, and additionally derives from
 stable_baselines3.common.vec_env.VecEnv when that package is importable so isinstance checks pass."""
 from __future__ import annotations
 
+import time
 from typing import Any, Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
@@ -46,8 +47,11 @@ class LazyInfos(Sequence):
     """infos without materialising N dicts per step: dicts are built on access.  `info` / `done` may be zero-argument callables
     (output="torch": nothing crosses PCIe, and the stream is not drained, unless somebody actually reads an info)."""
 
-    def __init__(self, info, done, terminal, still_valid=None):
+    def __init__(self, info, done, terminal, still_valid=None, episode=None):
         self._info, self._done, self._terminal = info, done, terminal
+        # episode_monitor=True: (returns [N], lengths [N], t) of every env's LAST finished episode, or a callable that fetches them;
+        # an env that is done in this step gets VecMonitor's infos[i]["episode"] = {"r", "l", "t"} from its row
+        self._episode = episode
         self._n = None if callable(done) else len(done)
         # output="torch": the terminal observations are VIEWS of the backend's terminal buffers, which hold the rows of the step that produced
         # these infos and are rewritten by the next one.  `still_valid()` turns a late read into an error instead of another step's rows.
@@ -60,6 +64,12 @@ class LazyInfos(Sequence):
                 self._terminal = self._terminal(self._done)
         return self._info, self._done
 
+    def _episode_of(self, i):
+        if callable(self._episode):
+            self._episode = self._episode()
+        r, l, t = self._episode
+        return {"r": float(r[i]), "l": int(l[i]), "t": t}
+
     def __len__(self):
         return len(self._host()[1]) if self._n is None else self._n
 
@@ -70,6 +80,8 @@ class LazyInfos(Sequence):
         r = info[i]
         d = {"agent_kills": int(r[0]), "allies_kills": int(r[1]), "deads": int(r[2]), "current_wave": int(r[3]),
              "TimeLimit.truncated": False}  # the reference always returns truncated=False (exp03_vFinal_environment.py:167)
+        if done[i] and self._episode is not None:
+            d["episode"] = self._episode_of(i)
         if done[i] and self._terminal is not None:
             if self._still_valid is not None and not self._still_valid():
                 raise RuntimeError("infos[i]['terminal_observation'] was read after a later step(): with output='torch' the terminal observations are "
@@ -98,18 +110,24 @@ class LazyInfos(Sequence):
         if self._terminal is not None:
             for i in np.flatnonzero(done):
                 out[i]["terminal_observation"] = {k: v[int(i)] for k, v in self._terminal.items()}
+        if self._episode is not None:
+            for i in np.flatnonzero(done):
+                out[i]["episode"] = self._episode_of(int(i))
         return out
 
 
 class ThreatEngageVecEnv(_SB3VecEnv):  # type: ignore[misc]
     """SB3 VecEnv API: reset / step_async / step_wait / step / close / seed / get_attr / set_attr /
     env_method / env_is_wrapped, attributes num_envs, observation_space, action_space, reset_infos,
-    render_mode.  Auto-reset with infos[i]["terminal_observation"] as SB3 expects."""
+    render_mode.  Auto-reset with infos[i]["terminal_observation"] as SB3 expects.
+    episode_monitor=True is SB3's VecMonitor built in: infos[i]["episode"] = {"r": return, "l": length, "t": seconds since
+    construction} for every env that finished an episode in that step (what SB3's PPO logger reads), kept on the device by
+    an EpisodeMonitor (monitor.py) and copied with the info rows the step copies anyway."""
 
     def __init__(self, task: str = "stage03", num_envs: int = 1024, device: str = "cuda:0",
                  dome_radius: Optional[float] = None, rl_frequency: int = 15, GUI: bool = False, seed: int = 0,
                  env_index_base: int = 0, output: str = "numpy", infos: str = "dicts", backend=None,
-                 persistent_obs: Optional[bool] = None, **overrides):
+                 persistent_obs: Optional[bool] = None, episode_monitor: bool = False, **overrides):
         if GUI:
             raise ValueError("GUI=True has no batched equivalent (the reference forces n_envs=1 with a PyBullet window)")
         if output not in ("numpy", "torch") or infos not in ("dicts", "lazy"):
@@ -141,6 +159,11 @@ class ThreatEngageVecEnv(_SB3VecEnv):  # type: ignore[misc]
         # exp05: the ally's driver (exp05_vFinal_environment.py:103-104); set with update_model / env_method("update_model", m)
         self.external_ally = int(self.cfg.ally_policy) == K.ALLY_EXTERNAL
         self.lw_driver = None
+        self.episode_monitor = None
+        if episode_monitor:
+            from .monitor import EpisodeMonitor
+            self.episode_monitor = EpisodeMonitor(self.num_envs, backend.device)
+            self._t_start = time.time()
 
     # ------------------------------------------------------------------ helpers
     def _to_host(self, tensors):
@@ -210,6 +233,8 @@ class ThreatEngageVecEnv(_SB3VecEnv):  # type: ignore[misc]
         self.reset_infos = [{} for _ in range(self.num_envs)]
         self._seeds = [None] * self.num_envs
         self._options = [{} for _ in range(self.num_envs)]
+        if self.episode_monitor is not None:
+            self.episode_monitor.reset()
         return self._obs(*obs)
 
     def step_async(self, actions) -> None:
@@ -223,6 +248,10 @@ class ThreatEngageVecEnv(_SB3VecEnv):  # type: ignore[misc]
             self._drive_ally()
         *obs_t, reward, done, info = (b.step_stacked if self.stacked else b.step)(self._actions, terminal=True)
         self._actions = None
+        mon, episode_t = self.episode_monitor, []
+        if mon is not None:   # last_ret / last_len of the envs that are done in this step are this step's episodes
+            mon.step(reward.contiguous(), done.contiguous(), info.contiguous())
+            episode_t, t_now = [mon.last_ret, mon.last_len], round(time.time() - self._t_start, 6)
         if self.stacked:
             obs_t = [obs_t[0], obs_t[1].bool(), obs_t[2], obs_t[3]]
         tbuf = ({"stacked_spheres": b.t_stacked, "validity_mask": b.t_mask.bool()} if self.stacked else {"lidar": b.t_lidar})
@@ -232,20 +261,26 @@ class ThreatEngageVecEnv(_SB3VecEnv):  # type: ignore[misc]
             # overwrites: their values of THIS step are copied now, asynchronously, into fresh pinned memory behind an event; an info indexed
             # later (a logger that drains afterwards, an asynchronous collector) waits for that event only and reads this step's values.
             host = {}
-            fetch = self._snapshot_async([info, done])
+            fetch = self._snapshot_async([info, done, *episode_t])
 
             def both():
                 if not host:
-                    host["info"], d = fetch()
+                    host["info"], d, *host["episode"] = fetch()
                     host["done"] = d.astype(bool)
                 return host
             gen = getattr(b, "generation", None)   # (backends without a step counter: no lifetime check)
             infos = LazyInfos(lambda: both()["info"], lambda: both()["done"], tbuf,
-                              still_valid=None if gen is None else (lambda: b.generation == gen))
+                              still_valid=None if gen is None else (lambda: b.generation == gen),
+                              episode=None if mon is None else (lambda: (*both()["episode"], t_now)))
             if self.infos_mode == "dicts":
                 infos = infos.materialise()
             return dict(zip(self._obs_keys(), obs_t)), reward, done.bool(), infos
-        *obs_np, rew, done_u8, info_np = self._to_host([*obs_t, reward, done, info])
+        host = self._to_host([*obs_t, reward, done, info, *episode_t])     # last_ret / last_len: 8 bytes per env next to the 4 KB observation
+        episode = None
+        if mon is not None:
+            *host, ep_r, ep_l = host
+            episode = (ep_r.copy(), ep_l.copy(), t_now)   # (a CPU stub's arrays are the monitor's own: keep this step's)
+        *obs_np, rew, done_u8, info_np = host
         done_np = done_u8.astype(bool)
         terminal = None
         if done_np.any():  # copy only the rows that are valid
@@ -255,7 +290,7 @@ class ThreatEngageVecEnv(_SB3VecEnv):  # type: ignore[misc]
             ti = torch.from_numpy(idx).to(b.device)
             rows = self._to_host([v[ti] for v in tbuf.values()])
             terminal = {k: _ScatterRows(idx, v, self.num_envs) for k, v in zip(tbuf.keys(), rows)}
-        infos = LazyInfos(info_np, done_np, terminal)
+        infos = LazyInfos(info_np, done_np, terminal, episode=episode)
         if self.infos_mode == "dicts":
             infos = infos.materialise()
         return dict(zip(self._obs_keys(), obs_np)), rew, done_np, infos

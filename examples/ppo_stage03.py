@@ -2,6 +2,7 @@
 """stage03 + PPO with everything on the GPU (BASELINE.json config 5): env shard, rollout storage, policy, update.
 
     python examples/ppo_stage03.py --envs 65536 --iters 5
+    python examples/ppo_stage03.py --envs 8192 --episode-stats --eval-episodes 200
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/ppo_stage03.py --envs 8192
 
 One process per GPU; each rank owns `--envs` environments (RNG keyed on the global env index) and the gradient
@@ -22,6 +23,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=32768)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--task", default="stage03")
+    ap.add_argument("--episode-stats", action="store_true", help="log ep_rew_mean, ep_len_mean, ... of the episodes that finished in each collect (rank-local)")
+    ap.add_argument("--eval-episodes", type=int, default=0, help="after training: evaluate the policy over N episodes on a fresh env (rank 0)")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -42,7 +45,7 @@ def main():
         else:
             dist.init_process_group(backend)
     env = BatchedEnv(default_config(args.task, n_envs=args.envs, env_index_base=rank * args.envs), dev)
-    ppo = PPO(env, PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, n_epochs=args.epochs), seed=0)
+    ppo = PPO(env, PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, n_epochs=args.epochs, episode_stats=args.episode_stats), seed=0)
     if rank == 0:
         print(f"rollout buffer {ppo.buf.bytes() / 2**30:.1f} GiB on {dev}; policy parameters {sum(p.numel() for p in ppo.policy.parameters())}", flush=True)
     for it in range(args.iters):
@@ -61,6 +64,12 @@ def main():
         dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         if rank == 0:
             print(json.dumps({"world": world, "replicas_in_sync": bool(torch.equal(lo, hi)), "param_abs_sum": float(flat.abs().sum())}), flush=True)
+    if args.eval_episodes > 0 and rank == 0:   # SB3's EvalCallback: a separate env, deterministic actions, raw rewards
+        from dronechase_amd.pipeline import ReinforcementLearningPipeline
+        eval_env = BatchedEnv(default_config(args.task, n_envs=min(args.envs, 1024), seed=1), dev)
+        avg, std, n, _ = ReinforcementLearningPipeline.evaluate(ppo, eval_env, n_eval_episodes=args.eval_episodes)
+        print(json.dumps({"eval_episodes": n, "eval_rew_mean": avg, "eval_rew_std": std}), flush=True)
+        eval_env.close()
     env.close()
     if world > 1:
         dist.destroy_process_group()

@@ -485,6 +485,53 @@ int te_policy_ppo_grad(const float* params, int32_t lidar_channels, int32_t n, c
                        const float* ret, const float* adv_mean_std, float clip_range, float vf_coef, float ent_coef, float* grad,
                        float* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Episode monitor: the bookkeeping of SB3's VecMonitor.step_wait (episode return and length per env, `infos[i]["episode"]`), of
+ * its logger's ep_rew_mean / ep_len_mean window, and of evaluate_policy's per-env episode quotas (what the reference's
+ * ReinforcementLearningPipeline.evaluate rests on, src/core/rl_framework/utils/pipeline.py:374-414), next to the step on the
+ * device instead of in Python on the host.
+ *
+ * A monitor is ONE caller-owned device buffer of te_monitor_bytes(n_envs, n_records) bytes, 16-byte aligned.  The calls take no
+ * te_env, allocate nothing, enqueue on `stream` only (no host synchronisation: a HIP graph can capture them) and run on the
+ * current device; the buffer is cloned and restored with a plain device copy.  Every call takes the same (mon, bytes, n_envs,
+ * n_records) the buffer was initialised with; every argument error (null pointer, n_envs <= 0, n_records < 0, bytes too small,
+ * misalignment) returns before anything is launched.
+ *
+ * te_monitor_step, after every te_step, with that step's reward [N] f32, done [N] u8 and info [N][4] i32 (16-byte aligned).
+ * For env e:  ret_e = ret_e + reward_e (one fp32 add per step, in step order: a host loop in float32 reproduces it bit for bit);
+ * len_e += 1; if done_e, the episode (ret_e, len_e, info_e) is complete (te_step computes info before the auto-reset, so the row
+ * of a done step is the ended episode's): it is added to the window accumulators, written to record slot offset_e + k_e if
+ * k_e < quota_e, k_e += 1, last_ret_e / last_len_e = (ret_e, len_e), and ret_e = len_e = 0.
+ * Quotas are evaluate_policy's: quota_e = (n_records + e) / N, i.e. with q = n_records / N and r = n_records % N,
+ * quota_e = q + (e >= N - r) and offset_e = e q + max(0, e - (N - r)): records are env-major, then by episode ordinal, and an env
+ * with short episodes contributes no more than its share.  n_records = 0 records nothing.
+ *
+ * Window accumulators (count, sum of len, sum of info[0..3] as int64; sum of ret and of ret^2 as double; min / max ret as float)
+ * are kept per wave of 64 envs, reduced in a fixed order: no float atomics, repeated runs are bitwise equal.  te_monitor_stats
+ * sums the waves' rows in a fixed order into *out (DEVICE memory, 8-byte aligned) and, with reset_window != 0, clears them; partial
+ * episodes, k_e and the records are kept.  min_ret / max_ret are 0 when count == 0.
+ *
+ * Buffer layout (byte offsets from te_monitor_layout; all arrays 16-byte aligned): word 0 = recorded (i32, the number of record
+ * slots written so far); rows [n_rows][72 bytes]; ret [N] f32, len [N] i32, episodes [N] i32 (k_e), last_ret [N] f32, last_len [N]
+ * i32; rec_info [R][4] i32, rec_ret [R] f32, rec_len [R] i32.  te_monitor_init zeroes the whole buffer. */
+typedef struct te_monitor_summary {
+  int64_t count, sum_len, sum_info[4];
+  double sum_ret, sum_ret2;
+  float min_ret, max_ret;
+  int32_t recorded, reserved;
+} te_monitor_summary;
+
+typedef struct te_monitor_offsets {
+  size_t bytes, n_rows, rows, ret, len, episodes, last_ret, last_len, rec_info, rec_ret, rec_len;
+} te_monitor_offsets;
+
+int te_monitor_bytes(int32_t n_envs, int32_t n_records, size_t* out_bytes);
+int te_monitor_layout(int32_t n_envs, int32_t n_records, te_monitor_offsets* out);
+int te_monitor_init(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, void* stream);
+int te_monitor_step(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, const float* reward, const uint8_t* done,
+                    const int32_t* info, void* stream);
+int te_monitor_stats(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, te_monitor_summary* out, int32_t reset_window,
+                     void* stream);
+
 int te_abi_version(void);
 const char* te_last_error(void);
 
