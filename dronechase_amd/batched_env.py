@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from . import config as K
+from .ppo import require_f32
 
 
 class BatchedEnv:
@@ -186,8 +187,8 @@ class BatchedEnv:
         lidar, inertial, last_action = self.wingman_scratch(wingman)
         if fused_policy.device != self.device:
             raise ValueError(f"drive_wingman: the policy lives on {fused_policy.device}, the env on {self.device}")
-        if mu is not None and (tuple(mu.shape) != (self.N, 4) or mu.dtype != torch.float32 or mu.device != self.device or not mu.is_contiguous()):
-            raise ValueError(f"drive_wingman: mu must be a contiguous float32 [{self.N}, 4] tensor on {self.device}")
+        if mu is not None:
+            require_f32("drive_wingman", "mu", mu, (self.N, 4), self.device, shown=f"[{self.N}, 4]")
         _lib.check(self.L.te_drive_wingman(self._h, int(wingman), self._p(fused_policy.params), int(fused_policy.lidar_channels), self._p(lidar),
                                            self._p(inertial), self._p(last_action), self._p(mu), self._stream()), "te_drive_wingman")
 

@@ -1220,6 +1220,28 @@ static hipError_t set_lds_limits(const KernelPlan& k) {   // dynamic LDS beyond 
   return hipSuccess;
 }
 
+// The launch of a policy kernel template's <2> or <3> instance (K2, K3: kernel(PolicyParams, args...)) on the tile grid of n rows.  kPolLdsBytes
+// is above the 64 KB a launch gets by default: opt in once per (device, instance, in `opted`); not a stream operation, so a capturing stream allows it.
+template <auto K2, auto K3, class... Args>
+static int policy_launch(int32_t lidar_channels, const float* params, int n, void* stream, const Args&... args) {
+  static uint64_t opted[2] = {0, 0};
+  uint64_t& bits = opted[lidar_channels - 2];
+  int dev = 0;
+  TE_HIP(hipGetDevice(&dev));
+  if (dev < 64 && !(bits >> dev & 1)) {
+    TE_HIP(hipFuncSetAttribute(lidar_channels == 3 ? reinterpret_cast<const void*>(K3) : reinterpret_cast<const void*>(K2),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes));
+    bits |= 1ull << dev;
+  }
+  PolicyParams P = policy_layout(lidar_channels);
+  P.base = params;
+  const dim3 grid((unsigned)((n + kPolTileM - 1) / kPolTileM));
+  if (lidar_channels == 3) hipLaunchKernelGGL(K3, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, args...);
+  else hipLaunchKernelGGL(K2, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, args...);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 __attribute__((visibility("default"))) const char* te_last_error(void) { return g_err.c_str(); }
@@ -1831,18 +1853,6 @@ __attribute__((visibility("default"))) int te_debug_stamps(te_env* e, uint64_t* 
   return 0;
 }
 
-// kPolLdsBytes is above the 64 KB a launch gets by default: opt in once per (device, kernel); not a stream operation, so a
-// capturing stream allows it.  `bits` is the kernel's own set of devices done.
-static int policy_lds_opt_in(const void* fn, uint64_t& bits) {
-  int dev = 0;
-  TE_HIP(hipGetDevice(&dev));
-  if (dev < 64 && !(bits >> dev & 1)) {
-    TE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes));
-    bits |= 1ull << dev;
-  }
-  return 0;
-}
-
 static int policy_words(int32_t lidar_channels, size_t* out) {
   if (lidar_channels != 2 && lidar_channels != 3) return fail("te_policy: lidar_channels must be 2 or 3");
   *out = (size_t)policy_layout(lidar_channels).words;
@@ -1867,18 +1877,8 @@ __attribute__((visibility("default"))) int te_policy_act(const float* params, in
   for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)eps, (const void*)mu, (const void*)value,
                         (const void*)action, (const void*)logp, (const void*)action_env})
     if ((uintptr_t)q & 3) return fail("te_policy_act: float arrays must be 4-byte aligned");
-  static uint64_t opted[2] = {0, 0};
-  if (policy_lds_opt_in(lidar_channels == 3 ? reinterpret_cast<const void*>(&policy_act_kernel<3>) : reinterpret_cast<const void*>(&policy_act_kernel<2>),
-                        opted[lidar_channels - 2]))
-    return 1;
-  PolicyParams P = policy_layout(lidar_channels);
-  P.base = params;
   const PolicyIO io{lidar, inertial, last_action, eps, mu, value, eps ? action : nullptr, eps ? logp : nullptr, eps ? action_env : nullptr, n};
-  const dim3 grid((unsigned)((n + kPolTileM - 1) / kPolTileM));
-  if (lidar_channels == 3) hipLaunchKernelGGL(policy_act_kernel<3>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, io);
-  else hipLaunchKernelGGL(policy_act_kernel<2>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, io);
-  TE_HIP(hipGetLastError());
-  return 0;
+  return policy_launch<&policy_act_kernel<2>, &policy_act_kernel<3>>(lidar_channels, params, n, stream, io);
 }
 
 __attribute__((visibility("default"))) int te_drive_wingman(te_env* e, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar,
@@ -1894,83 +1894,9 @@ __attribute__((visibility("default"))) int te_drive_wingman(te_env* e, int32_t w
   if (((uintptr_t)lidar & 15) || ((uintptr_t)last_action & 15)) return fail("te_drive_wingman: lidar and last_action must be 16-byte aligned");
   if (((uintptr_t)inertial & 3) || ((uintptr_t)mu & 3)) return fail("te_drive_wingman: inertial and mu must be 4-byte aligned");
   DeviceGuard guard(e->device);
-  static uint64_t opted[2] = {0, 0};
-  if (policy_lds_opt_in(lidar_channels == 3 ? reinterpret_cast<const void*>(&policy_drive_kernel<3>) : reinterpret_cast<const void*>(&policy_drive_kernel<2>),
-                        opted[lidar_channels - 2]))
-    return 1;
   if (te_observe_wingman(e, wingman, lidar, inertial, last_action, nullptr, stream)) return 1;
-  PolicyParams P = policy_layout(lidar_channels);
-  P.base = params;
   const PolicyIn in{lidar, inertial, last_action, nullptr, e->p.N};
-  const dim3 grid((unsigned)((e->p.N + kPolTileM - 1) / kPolTileM));
-  if (lidar_channels == 3) hipLaunchKernelGGL(policy_drive_kernel<3>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, in, e->p, (int)wingman, mu);
-  else hipLaunchKernelGGL(policy_drive_kernel<2>, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, in, e->p, (int)wingman, mu);
-  TE_HIP(hipGetLastError());
-  return 0;
-}
-
-// The workspace of te_policy_ppo_grad for n rows (Bp = n rounded up to the tile): every layer's input X [R][K] and pre-activation
-// gradient dZ [R][N] row-major, R = Bp (x 12 conv1 positions, x 3 conv2 columns), then the split-K partials.  With ws == NULL
-// only the size is computed; otherwise the tile kernel's pointers and the split-K plan are filled in.
-static size_t policy_grad_layout(int C, int n, char* ws, const PolicyParams& P, float* grad, float* stats, GradTileArgs* ta, GradPlan* gp) {
-  const size_t Bp = ((size_t)n + kPolTileM - 1) / kPolTileM * kPolTileM;
-  size_t off = 0;
-  auto take = [&](size_t rows, int cols) {
-    float* at = ws ? reinterpret_cast<float*>(ws + off) : nullptr;
-    off += (rows * cols * sizeof(float) + 255) / 256 * 256;
-    return at;
-  };
-  GradTileArgs t{};
-  struct Sv { int buf, pos, ld; };
-  const Sv svs[] = {{POL_SV_C1X, 12, 16 * C}, {POL_SV_C2X, 3, 128}, {POL_SV_IN0X, 1, 15}, {POL_SV_IN1X, 1, 128}, {POL_SV_IN2X, 1, 128},
-                    {POL_SV_AC0X, 1, 4}, {POL_SV_AC1X, 1, 128}, {POL_SV_AC2X, 1, 128}, {POL_SV_FX, 1, 448}, {POL_SV_F, 1, 256},
-                    {POL_SV_PI1X, 1, 64}, {POL_SV_MUX, 1, 64}, {POL_SV_VF1X, 1, 64}, {POL_SV_VX, 1, 64}};
-  for (const Sv& v : svs) {
-    t.save[v.buf] = take(Bp * v.pos, v.ld);
-    t.save_pos[v.buf] = v.pos;
-    t.save_ld[v.buf] = v.ld;
-  }
-  t.dz_c1 = take(Bp * 12, 32); t.dz_c2 = take(Bp * 3, 64);
-  for (int i = 0; i < 3; ++i) t.dz_in[i] = take(Bp, 128);
-  for (int i = 0; i < 3; ++i) t.dz_ac[i] = take(Bp, 128);
-  t.dz_f = take(Bp, 256);
-  for (int i = 0; i < 2; ++i) t.dz_pi[i] = take(Bp, 64);
-  for (int i = 0; i < 2; ++i) t.dz_vf[i] = take(Bp, 64);
-  t.dz_mu = take(Bp, 4); t.dz_v = take(Bp, 1); t.dls = take(Bp, 4); t.st = take(Bp, 4);
-
-  GradPlan g{};
-  struct Ly { const float* dz; const float* x; int N, K, pos, w, b; };
-  const int none = -1;
-  const Ly ls[kGradLayers] = {
-      {t.dz_c1, t.save[POL_SV_C1X], 32, 16 * C, 12, P.c1w, P.c1b}, {t.dz_c2, t.save[POL_SV_C2X], 64, 128, 3, P.c2w, P.c2b},
-      {t.dz_in[0], t.save[POL_SV_IN0X], 128, 15, 1, P.in_w[0], P.in_b[0]}, {t.dz_in[1], t.save[POL_SV_IN1X], 128, 128, 1, P.in_w[1], P.in_b[1]},
-      {t.dz_in[2], t.save[POL_SV_IN2X], 128, 128, 1, P.in_w[2], P.in_b[2]}, {t.dz_ac[0], t.save[POL_SV_AC0X], 128, 4, 1, P.ac_w[0], P.ac_b[0]},
-      {t.dz_ac[1], t.save[POL_SV_AC1X], 128, 128, 1, P.ac_w[1], P.ac_b[1]}, {t.dz_ac[2], t.save[POL_SV_AC2X], 128, 128, 1, P.ac_w[2], P.ac_b[2]},
-      {t.dz_f, t.save[POL_SV_FX], 256, 448, 1, P.fw, P.fb},
-      {t.dz_pi[0], t.save[POL_SV_F], 64, 256, 1, P.pi_w[0], P.pi_b[0]}, {t.dz_pi[1], t.save[POL_SV_PI1X], 64, 64, 1, P.pi_w[1], P.pi_b[1]},
-      {t.dz_vf[0], t.save[POL_SV_F], 64, 256, 1, P.vf_w[0], P.vf_b[0]}, {t.dz_vf[1], t.save[POL_SV_VF1X], 64, 64, 1, P.vf_w[1], P.vf_b[1]},
-      {t.dz_mu, t.save[POL_SV_MUX], 4, 64, 1, P.muw, P.mub}, {t.dz_v, t.save[POL_SV_VX], 1, 64, 1, P.vw, P.vb},
-      {t.dls, nullptr, 4, 0, 1, none, P.log_std}, {t.st, nullptr, 4, 0, 1, none, none}};
-  int wgs = 0, words = 0;
-  for (int l = 0; l < kGradLayers; ++l) {
-    const Ly& y = ls[l];
-    GradLayer& L = g.L[l];
-    L.dz = y.dz; L.x = y.x; L.N = y.N; L.K = y.K; L.R = (int)(Bp * y.pos);
-    L.ntiles = (y.N + kGradTile - 1) / kGradTile;
-    L.ktiles = (y.K + 1 + kGradTile - 1) / kGradTile;
-    L.slices = (L.R + kGradSlice - 1) / kGradSlice;
-    L.wg0 = wgs; L.word0 = words;
-    wgs += L.slices * L.ntiles * L.ktiles;
-    words += y.N * (y.K + 1);
-    L.part = take((size_t)L.slices * y.N, y.K + 1);
-    L.w_out = grad && y.w != none ? grad + y.w : nullptr;
-    L.b_out = l == kGradLayers - 1 ? stats : (grad ? grad + y.b : nullptr);
-    L.scale = l == kGradLayers - 1 ? 1.f / (float)n : 1.f;   // the statistics are means over the n rows
-  }
-  g.wgs = wgs; g.words = words;
-  if (ta) *ta = t;
-  if (gp) *gp = g;
-  return off;
+  return policy_launch<&policy_drive_kernel<2>, &policy_drive_kernel<3>>(lidar_channels, params, e->p.N, stream, in, e->p, (int)wingman, mu);
 }
 
 // n up to 2^27: the conv1 layer's 12 * n reduction rows stay within int
@@ -2005,28 +1931,17 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* param
   for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)action, (const void*)old_logp, (const void*)adv,
                         (const void*)ret, (const void*)adv_mean_std, (const void*)stats})
     if ((uintptr_t)q & 3) return fail("te_policy_ppo_grad: float arrays must be 4-byte aligned");
-  PolicyParams P = policy_layout(lidar_channels);
-  P.base = params;
-  GradTileArgs t;
-  GradPlan g;
-  const size_t need = policy_grad_layout(lidar_channels, n, static_cast<char*>(workspace), P, grad, stats, &t, &g);
+  GradTileArgs t; GradPlan g;
+  const size_t need = policy_grad_layout(lidar_channels, n, static_cast<char*>(workspace), policy_layout(lidar_channels), grad, stats, &t, &g);
   if (workspace_bytes < need)
     return fail("te_policy_ppo_grad: workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_policy_grad_workspace_bytes says " +
                 std::to_string(need) + ")");
   if (!std::isfinite(clip_range) || clip_range < 0.f) return fail("te_policy_ppo_grad: clip_range must be finite and >= 0");
-  static uint64_t opted[2] = {0, 0};
-  if (policy_lds_opt_in(lidar_channels == 3 ? reinterpret_cast<const void*>(&policy_grad_tile_kernel<3>)
-                                            : reinterpret_cast<const void*>(&policy_grad_tile_kernel<2>),
-                        opted[lidar_channels - 2]))
-    return 1;
   t.action = action; t.old_logp = old_logp; t.adv = adv; t.ret = ret; t.adv_mean_std = adv_mean_std;
   t.clip = clip_range; t.vf_coef = vf_coef; t.ent_coef = ent_coef; t.inv_n = 1.f / (float)n;
   const PolicyIn in{lidar, inertial, last_action, index, n};
   const hipStream_t s = (hipStream_t)stream;
-  const dim3 tiles((unsigned)((n + kPolTileM - 1) / kPolTileM));
-  if (lidar_channels == 3) hipLaunchKernelGGL(policy_grad_tile_kernel<3>, tiles, dim3(kPolThreads), kPolLdsBytes, s, P, in, t);
-  else hipLaunchKernelGGL(policy_grad_tile_kernel<2>, tiles, dim3(kPolThreads), kPolLdsBytes, s, P, in, t);
-  TE_HIP(hipGetLastError());
+  if (policy_launch<&policy_grad_tile_kernel<2>, &policy_grad_tile_kernel<3>>(lidar_channels, params, n, stream, in, t)) return 1;
   hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);

@@ -39,30 +39,64 @@ static_assert(kPolTileM * kPolFS <= kPolUWords, "trunk tile fits the ping-pong r
 static_assert(2 * kPolTileM * kPolPS + kPolTileM * 4 <= kPolZWords, "head tiles fit the feature region");
 constexpr int kPolLdsBytes = (kPolZWords + kPolUWords) * 4;
 
-// Float offsets of every tensor in the packed parameter buffer (the public layout of threatengage.h).
+// What pol_forward hands to its `save` hook besides keeping it in LDS: every layer's input, i.e. what the weight gradient of that
+// layer needs.  save(buf, m, sub, col, v): tile row m, sub-row sub (a conv position), column col.
+enum {
+  POL_SV_C1X = 0,   // conv1 patches: sub = conv1 position p = ow2 * 4 + oh * 2 + j (0..11), col = c * 16 + kh * 4 + kw
+  POL_SV_C2X,       // conv2 patches (conv1 output after ReLU): sub = ow2 (0..2), col = ci * 4 + kh * 2 + kw
+  POL_SV_IN0X, POL_SV_IN1X, POL_SV_IN2X,   // inputs of inertial.{0,2,4}: [15], [128], [128]
+  POL_SV_AC0X, POL_SV_AC1X, POL_SV_AC2X,   // inputs of action.{0,2,4}: [4], [128], [128]
+  POL_SV_FX,        // the concat [448] (conv2 output in flatten order co * 3 + ow2, inertial, last_action): input of final.0
+  POL_SV_F,         // the trunk [256]: input of pi.0 and vf.0
+  POL_SV_PI1X, POL_SV_MUX, POL_SV_VF1X, POL_SV_VX,   // [64] each: inputs of pi.2, mu, vf.2, value
+  POL_SV_COUNT
+};
+
+// The 15 weight layers in the order of the packed parameter buffer, then the two bias-only pseudo-layers of the gradient's split-K
+// reduction (te_policy_grad.hpp): d loss / d log_std [4] and the statistics [pg, vl, ent, clip_frac].
+enum {
+  POL_L_C1 = 0, POL_L_C2, POL_L_IN0, POL_L_IN1, POL_L_IN2, POL_L_AC0, POL_L_AC1, POL_L_AC2, POL_L_F,
+  POL_L_PI0, POL_L_PI1, POL_L_VF0, POL_L_VF1, POL_L_MU, POL_L_V,
+  POL_L_WEIGHTS, POL_L_LOGSTD = POL_L_WEIGHTS, POL_L_STATS, POL_L_COUNT
+};
+
+// The one description of the network: layer l computes N outputs from K inputs at each of its `pos` positions per sample (a conv's
+// output positions; 1 for a Linear) and reads its input from saved buffer x.  The packed layout, the saved inputs' geometry, the
+// gradient workspace and the split-K plan are all derived from this table.
+struct PolLayer { int N, K, pos, x; };
+
+__host__ __device__ constexpr PolLayer pol_layer(int l, int C) {
+  const PolLayer t[POL_L_COUNT] = {
+      {32, 16 * C, 12, POL_SV_C1X}, {64, 128, 3, POL_SV_C2X},
+      {128, 15, 1, POL_SV_IN0X},    {128, 128, 1, POL_SV_IN1X}, {128, 128, 1, POL_SV_IN2X},
+      {128, 4, 1, POL_SV_AC0X},     {128, 128, 1, POL_SV_AC1X}, {128, 128, 1, POL_SV_AC2X},
+      {256, 448, 1, POL_SV_FX},
+      {64, 256, 1, POL_SV_F},       {64, 64, 1, POL_SV_PI1X},
+      {64, 256, 1, POL_SV_F},       {64, 64, 1, POL_SV_VF1X},
+      {4, 64, 1, POL_SV_MUX},       {1, 64, 1, POL_SV_VX},
+      {4, 0, 1, POL_SV_COUNT},      {4, 0, 1, POL_SV_COUNT}};   // log_std and the statistics: no input
+  return t[l];
+}
+static_assert(pol_layer(POL_L_PI0, 3).K == pol_layer(POL_L_VF0, 3).K && pol_layer(POL_L_PI0, 3).pos == pol_layer(POL_L_VF0, 3).pos, "POL_SV_F feeds both");
+
+// Float offsets of every tensor in the packed parameter buffer (the public layout of threatengage.h): per layer the weight
+// [N][K], then the bias [N]; log_std last.  A kernel argument by value: index `at` with compile-time constants only, or it leaves the SGPRs.
 struct PolicyParams {
   const float* base;
-  int c1w, c1b, c2w, c2b;
-  int in_w[3], in_b[3], ac_w[3], ac_b[3];
-  int fw, fb, pi_w[2], pi_b[2], vf_w[2], vf_b[2], muw, mub, vw, vb, log_std;
-  int words;
+  struct { int w, b; } at[POL_L_WEIGHTS];
+  int log_std, words;
 };
 
 inline PolicyParams policy_layout(int C) {
   PolicyParams p{};
   int o = 0;
-  auto take = [&](int n) { int at = o; o += n; return at; };
-  p.c1w = take(32 * 16 * C); p.c1b = take(32);
-  p.c2w = take(64 * 128);    p.c2b = take(64);
-  for (int i = 0; i < 3; ++i) { p.in_w[i] = take(128 * (i ? 128 : 15)); p.in_b[i] = take(128); }
-  for (int i = 0; i < 3; ++i) { p.ac_w[i] = take(128 * (i ? 128 : 4)); p.ac_b[i] = take(128); }
-  p.fw = take(256 * 448); p.fb = take(256);
-  for (int i = 0; i < 2; ++i) { p.pi_w[i] = take(64 * (i ? 64 : 256)); p.pi_b[i] = take(64); }
-  for (int i = 0; i < 2; ++i) { p.vf_w[i] = take(64 * (i ? 64 : 256)); p.vf_b[i] = take(64); }
-  p.muw = take(4 * 64); p.mub = take(4);
-  p.vw = take(64); p.vb = take(1);
-  p.log_std = take(4);
-  p.words = o;
+  for (int l = 0; l < POL_L_WEIGHTS; ++l) {
+    const PolLayer y = pol_layer(l, C);
+    p.at[l].w = o; o += y.N * y.K;
+    p.at[l].b = o; o += y.N;
+  }
+  p.log_std = o;
+  p.words = o + pol_layer(POL_L_LOGSTD, C).N;
   return p;
 }
 
@@ -141,18 +175,12 @@ TE_DEV void pol_dense(const float* X, int ldx, const float* __restrict__ W, cons
       [=](int m, int n, float v) { store(m, n, ACT == POL_RELU ? fmaxf(v, 0.f) : tanhf(v)); });
 }
 
-// What pol_forward hands to its `save` hook besides keeping it in LDS: every layer's input, i.e. what the weight gradient of that
-// layer needs.  save(buf, m, sub, col, v): tile row m, sub-row sub (a conv position), column col.
-enum {
-  POL_SV_C1X = 0,   // conv1 patches: sub = conv1 position p = ow2 * 4 + oh * 2 + j (0..11), col = c * 16 + kh * 4 + kw
-  POL_SV_C2X,       // conv2 patches (conv1 output after ReLU): sub = ow2 (0..2), col = ci * 4 + kh * 2 + kw
-  POL_SV_IN0X, POL_SV_IN1X, POL_SV_IN2X,   // inputs of inertial.{0,2,4}: [15], [128], [128]
-  POL_SV_AC0X, POL_SV_AC1X, POL_SV_AC2X,   // inputs of action.{0,2,4}: [4], [128], [128]
-  POL_SV_FX,        // the concat [448] (conv2 output in flatten order co * 3 + ow2, inertial, last_action): input of final.0
-  POL_SV_F,         // the trunk [256]: input of pi.0 and vf.0
-  POL_SV_PI1X, POL_SV_MUX, POL_SV_VF1X, POL_SV_VX,   // [64] each: inputs of pi.2, mu, vf.2, value
-  POL_SV_COUNT
-};
+// The forward of weight layer L on its packed weight and bias.
+template <int L, int C, int ACT, class Store>
+TE_DEV void pol_linear(const PolicyParams& P, const float* X, int ldx, Store store) {
+  constexpr PolLayer y = pol_layer(L, C);
+  pol_dense<y.K, y.N, ACT>(X, ldx, P.base + P.at[L].w, P.base + P.at[L].b, store);
+}
 
 struct PolNoSave {
   TE_DEV void operator()(int, int, int, int, float) const {}
@@ -178,7 +206,8 @@ TE_DEV void pol_forward(const PolicyParams& P, const PolicyIn& in, float* pol_ld
   const float* __restrict__ prm = P.base;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, h = lane >> 4;
   auto src = [&](int row) -> size_t { return in.index ? (size_t)in.index[row] : (size_t)row; };
-  auto to = [=](float* Y, int ld, int sv) { return [=](int m, int n, float v) { Y[m * ld + n] = v; save(sv, m, 0, n, v); }; };
+  // next: the layer that reads this output, from its saved buffer
+  auto to = [=](float* Y, int ld, int next) { return [=](int m, int n, float v) { Y[m * ld + n] = v; save(pol_layer(next, C).x, m, 0, n, v); }; };
 
   // ---- LIDAR: conv1 + conv2, one conv2 output column (ow2) at a time
   {
@@ -189,7 +218,7 @@ TE_DEV void pol_forward(const PolicyParams& P, const PolicyIn& in, float* pol_ld
       pol_f32x4 acc[2][2];
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
-        const float b = prm[P.c1b + nt * 16 + r];
+        const float b = prm[P.at[POL_L_C1].b + nt * 16 + r];
         acc[0][nt] = pol_f32x4{b, b, b, b}; acc[1][nt] = acc[0][nt];
       }
 #pragma unroll
@@ -209,7 +238,7 @@ TE_DEV void pol_forward(const PolicyParams& P, const PolicyIn& in, float* pol_ld
           save(POL_SV_C1X, m, p, col + 2, a[half].z); save(POL_SV_C1X, m, p, col + 3, a[half].w);
         }
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) w[nt] = *reinterpret_cast<const float4*>(prm + P.c1w + (nt * 16 + r) * (16 * C) + c * 16 + 4 * h);
+        for (int nt = 0; nt < 2; ++nt) w[nt] = *reinterpret_cast<const float4*>(prm + P.at[POL_L_C1].w + (nt * 16 + r) * (16 * C) + c * 16 + 4 * h);
 #pragma unroll
         for (int half = 0; half < 2; ++half)
 #pragma unroll
@@ -228,8 +257,8 @@ TE_DEV void pol_forward(const PolicyParams& P, const PolicyIn& in, float* pol_ld
             save(POL_SV_C2X, m, ow2, col, v);
           }
       __syncthreads();
-      pol_dense<128, 64, POL_RELU>(T1, kPolTS, prm + P.c2w, prm + P.c2b,
-                                   [=](int m, int n, float v) { Z[m * kPolZS + n * 3 + ow2] = v; save(POL_SV_FX, m, 0, n * 3 + ow2, v); });
+      pol_linear<POL_L_C2, C, POL_RELU>(P, T1, kPolTS,
+                                        [=](int m, int n, float v) { Z[m * kPolZS + n * 3 + ow2] = v; save(POL_SV_FX, m, 0, n * 3 + ow2, v); });
       __syncthreads();
     }
   }
@@ -246,48 +275,49 @@ TE_DEV void pol_forward(const PolicyParams& P, const PolicyIn& in, float* pol_ld
   }
   __syncthreads();
   // each chain ping-pongs between its own 128 columns of Z and T1 (T2 holds last_action's input until its first layer)
-  auto toZ = [=](int col0, int sv) {
+  auto toZ = [=](int col0, int next) {
+    const int sv = pol_layer(next, C).x;
     return [=](int m, int n, float v) { Z[m * kPolZS + col0 + n] = v; save(sv, m, 0, sv == POL_SV_FX ? col0 + n : n, v); };
   };
-  pol_dense<15, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[0], prm + P.in_b[0], toZ(192, POL_SV_IN1X));
+  pol_linear<POL_L_IN0, C, POL_RELU>(P, T1, kPolTS, toZ(192, POL_L_IN1));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(Z + 192, kPolZS, prm + P.in_w[1], prm + P.in_b[1], to(T1, kPolTS, POL_SV_IN2X));
+  pol_linear<POL_L_IN1, C, POL_RELU>(P, Z + 192, kPolZS, to(T1, kPolTS, POL_L_IN2));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.in_w[2], prm + P.in_b[2], toZ(192, POL_SV_FX));
+  pol_linear<POL_L_IN2, C, POL_RELU>(P, T1, kPolTS, toZ(192, POL_L_F));
   __syncthreads();
-  pol_dense<4, 128, POL_RELU>(T2, kPolTS, prm + P.ac_w[0], prm + P.ac_b[0], toZ(320, POL_SV_AC1X));
+  pol_linear<POL_L_AC0, C, POL_RELU>(P, T2, kPolTS, toZ(320, POL_L_AC1));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(Z + 320, kPolZS, prm + P.ac_w[1], prm + P.ac_b[1], to(T1, kPolTS, POL_SV_AC2X));
+  pol_linear<POL_L_AC1, C, POL_RELU>(P, Z + 320, kPolZS, to(T1, kPolTS, POL_L_AC2));
   __syncthreads();
-  pol_dense<128, 128, POL_RELU>(T1, kPolTS, prm + P.ac_w[2], prm + P.ac_b[2], toZ(320, POL_SV_FX));
+  pol_linear<POL_L_AC2, C, POL_RELU>(P, T1, kPolTS, toZ(320, POL_L_F));
   __syncthreads();
 
   // ---- trunk: concat [448] -> Linear(256) + ReLU
-  pol_dense<448, 256, POL_RELU>(Z, kPolZS, prm + P.fw, prm + P.fb, to(F, kPolFS, POL_SV_F));
+  pol_linear<POL_L_F, C, POL_RELU>(P, Z, kPolZS, to(F, kPolFS, POL_L_PI0));
   __syncthreads();
 
   // ---- pi head, then mu (one thread per row)
-  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.pi_w[0], prm + P.pi_b[0], to(P1, kPolPS, POL_SV_PI1X));
+  pol_linear<POL_L_PI0, C, POL_TANH>(P, F, kPolFS, to(P1, kPolPS, POL_L_PI1));
   __syncthreads();
-  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.pi_w[1], prm + P.pi_b[1], to(P2, kPolPS, POL_SV_MUX));
+  pol_linear<POL_L_PI1, C, POL_TANH>(P, P1, kPolPS, to(P2, kPolPS, POL_L_MU));
   __syncthreads();
   if (tid < kPolTileM) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-      float s = prm[P.mub + a];
-      for (int k = 0; k < 64; ++k) s = fmaf(P2[tid * kPolPS + k], prm[P.muw + a * 64 + k], s);
+      float s = prm[P.at[POL_L_MU].b + a];
+      for (int k = 0; k < 64; ++k) s = fmaf(P2[tid * kPolPS + k], prm[P.at[POL_L_MU].w + a * 64 + k], s);
       MU[tid * 4 + a] = s;
     }
   }
   __syncthreads();
   // ---- vf head, then value (the thread that computed mu computes the value: no barrier needed)
-  pol_dense<256, 64, POL_TANH>(F, kPolFS, prm + P.vf_w[0], prm + P.vf_b[0], to(P1, kPolPS, POL_SV_VF1X));
+  pol_linear<POL_L_VF0, C, POL_TANH>(P, F, kPolFS, to(P1, kPolPS, POL_L_VF1));
   __syncthreads();
-  pol_dense<64, 64, POL_TANH>(P1, kPolPS, prm + P.vf_w[1], prm + P.vf_b[1], to(P2, kPolPS, POL_SV_VX));
+  pol_linear<POL_L_VF1, C, POL_TANH>(P, P1, kPolPS, to(P2, kPolPS, POL_L_V));
   __syncthreads();
   if (tid < kPolTileM) {
-    float v = prm[P.vb];
-    for (int k = 0; k < 64; ++k) v = fmaf(P2[tid * kPolPS + k], prm[P.vw + k], v);
+    float v = prm[P.at[POL_L_V].b];
+    for (int k = 0; k < 64; ++k) v = fmaf(P2[tid * kPolPS + k], prm[P.at[POL_L_V].w + k], v);
     VAL[tid] = v;
   }
 }

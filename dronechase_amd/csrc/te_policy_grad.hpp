@@ -26,6 +26,7 @@ constexpr int kGradTile = 64;         // output tile of policy_wgrad_kernel: 64 
 constexpr int kGradStep = 32;         // rows staged in LDS per step
 constexpr int kGradLS = kGradStep + 4;
 constexpr int kGradLayers = 17;       // 15 weight layers, log_std, the statistics
+static_assert(kGradLayers == POL_L_COUNT, "one split-K layer per row of pol_layer's table");
 
 // One layer of the split-K reduction: partial[slice][N][K + 1] of dZ[R][N]^T [X[R][K] | 1].  Row counts R are multiples of 32.
 struct GradLayer {
@@ -43,11 +44,12 @@ struct GradPlan {
   int wgs, words;
 };
 
-// The workspace pointers of the tile kernel and the per-row inputs of the loss.
+// The workspace pointers of the tile kernel (dz[l]: layer POL_L_l's dZ [R][N]; the pseudo-layers' per-row terms) and the per-row inputs
+// of the loss.  Like PolicyParams a kernel argument by value: index its arrays with compile-time constants only, or it leaves the SGPRs.
 struct GradTileArgs {
   float* save[POL_SV_COUNT];
   int save_ld[POL_SV_COUNT], save_pos[POL_SV_COUNT];
-  float *dz_c1, *dz_c2, *dz_in[3], *dz_ac[3], *dz_f, *dz_pi[2], *dz_vf[2], *dz_mu, *dz_v, *dls, *st;
+  float* dz[POL_L_COUNT];
   const float *action, *old_logp, *adv, *ret, *adv_mean_std;
   float clip, vf_coef, ent_coef, inv_n;
 };
@@ -68,6 +70,14 @@ TE_DEV auto pol_wT(const float* __restrict__ W) {
   };
 }
 
+// The backward of weight layer L to its input: epi(m, k, dX[m][k]) of dX[32][K] = dZ[32][N] W.  (l: the layer whose weight is
+// read, of L's shape; a constant once the caller's loop is unrolled.)
+template <int L, int C, class Epi>
+TE_DEV void pol_linear_back(const PolicyParams& P, const float* dZ, int ld, Epi epi, int l = L) {
+  constexpr PolLayer y = pol_layer(L, C);
+  pol_gemm<y.N, y.K>(dZ, ld, pol_wT<y.K>(P.base + P.at[l].w), [](int) { return 0.f; }, epi);
+}
+
 template <int C>
 __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyParams P, PolicyIn in, GradTileArgs g) {
   extern __shared__ __attribute__((aligned(16))) float pol_lds[];
@@ -86,7 +96,6 @@ __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyPar
   float* T2 = T1 + kPolTileM * kPolTS;
   static_assert(2 * kPolTileM * kPolPS + kPolTileM * 10 <= kPolZWords, "head tiles, MU, VAL, DMU and DV fit the feature region");
   auto at = [&](int sv, int m, int sub, int col) { return g.save[sv][((size_t)(row0 + m) * g.save_pos[sv] + sub) * g.save_ld[sv] + col]; };
-  auto zero = [](int) { return 0.f; };
 
   // ---- the loss of each row (thread tid = row: mu and value are its own)
   if (tid < kPolTileM) {
@@ -124,12 +133,12 @@ __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyPar
 #pragma unroll
     for (int a = 0; a < 4; ++a) {     // padding rows (row >= n) get zeros: everything downstream of them is exactly 0
       DMU[tid * 4 + a] = dmu[a];
-      g.dz_mu[(size_t)row * 4 + a] = dmu[a];
-      g.dls[(size_t)row * 4 + a] = dls[a];
-      g.st[(size_t)row * 4 + a] = st[a];
+      g.dz[POL_L_MU][(size_t)row * 4 + a] = dmu[a];
+      g.dz[POL_L_LOGSTD][(size_t)row * 4 + a] = dls[a];
+      g.dz[POL_L_STATS][(size_t)row * 4 + a] = st[a];
     }
     DV[tid] = dv;
-    g.dz_v[row] = dv;
+    g.dz[POL_L_V][row] = dv;
   }
   __syncthreads();
 
@@ -138,66 +147,67 @@ __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyPar
     const int m = t >> 6, k = t & 63;
     float d = 0.f;
 #pragma unroll
-    for (int a = 0; a < 4; ++a) d = fmaf(DMU[m * 4 + a], prm[P.muw + a * 64 + k], d);
+    for (int a = 0; a < 4; ++a) d = fmaf(DMU[m * 4 + a], prm[P.at[POL_L_MU].w + a * 64 + k], d);
     const float y = at(POL_SV_MUX, m, 0, k), dz = d * (1.f - y * y);
     HA[m * kPolPS + k] = dz;
-    g.dz_pi[1][(size_t)(row0 + m) * 64 + k] = dz;
+    g.dz[POL_L_PI1][(size_t)(row0 + m) * 64 + k] = dz;
   }
   __syncthreads();
-  pol_gemm<64, 64>(HA, kPolPS, pol_wT<64>(prm + P.pi_w[1]), zero, [&](int m, int n, float v) {
+  pol_linear_back<POL_L_PI1, C>(P, HA, kPolPS, [&](int m, int n, float v) {
     const float y = at(POL_SV_PI1X, m, 0, n), dz = v * (1.f - y * y);
     HB[m * kPolPS + n] = dz;
-    g.dz_pi[0][(size_t)(row0 + m) * 64 + n] = dz;
+    g.dz[POL_L_PI0][(size_t)(row0 + m) * 64 + n] = dz;
   });
   __syncthreads();
-  pol_gemm<64, 256>(HB, kPolPS, pol_wT<256>(prm + P.pi_w[0]), zero, [&](int m, int n, float v) { DF[m * kPolFS + n] = v; });
+  pol_linear_back<POL_L_PI0, C>(P, HB, kPolPS, [&](int m, int n, float v) { DF[m * kPolFS + n] = v; });
   __syncthreads();
   for (int t = tid; t < kPolTileM * 64; t += kPolThreads) {
     const int m = t >> 6, k = t & 63;
-    const float y = at(POL_SV_VX, m, 0, k), dz = DV[m] * prm[P.vw + k] * (1.f - y * y);
+    const float y = at(POL_SV_VX, m, 0, k), dz = DV[m] * prm[P.at[POL_L_V].w + k] * (1.f - y * y);
     HA[m * kPolPS + k] = dz;
-    g.dz_vf[1][(size_t)(row0 + m) * 64 + k] = dz;
+    g.dz[POL_L_VF1][(size_t)(row0 + m) * 64 + k] = dz;
   }
   __syncthreads();
-  pol_gemm<64, 64>(HA, kPolPS, pol_wT<64>(prm + P.vf_w[1]), zero, [&](int m, int n, float v) {
+  pol_linear_back<POL_L_VF1, C>(P, HA, kPolPS, [&](int m, int n, float v) {
     const float y = at(POL_SV_VF1X, m, 0, n), dz = v * (1.f - y * y);
     HB[m * kPolPS + n] = dz;
-    g.dz_vf[0][(size_t)(row0 + m) * 64 + n] = dz;
+    g.dz[POL_L_VF0][(size_t)(row0 + m) * 64 + n] = dz;
   });
   __syncthreads();
-  pol_gemm<64, 256>(HB, kPolPS, pol_wT<256>(prm + P.vf_w[0]), zero, [&](int m, int n, float v) {
+  pol_linear_back<POL_L_VF0, C>(P, HB, kPolPS, [&](int m, int n, float v) {
     const float dz = at(POL_SV_F, m, 0, n) > 0.f ? DF[m * kPolFS + n] + v : 0.f;
     DF[m * kPolFS + n] = dz;
-    g.dz_f[(size_t)(row0 + m) * 256 + n] = dz;
+    g.dz[POL_L_F][(size_t)(row0 + m) * 256 + n] = dz;
   });
   __syncthreads();
 
   // ---- trunk -> the concat: conv2 columns 0..191 (flatten order co * 3 + ow2), inertial 192..319, last_action 320..447
-  pol_gemm<256, 448>(DF, kPolFS, pol_wT<448>(prm + P.fw), zero, [&](int m, int n, float v) {
+  pol_linear_back<POL_L_F, C>(P, DF, kPolFS, [&](int m, int n, float v) {
     const float dz = at(POL_SV_FX, m, 0, n) > 0.f ? v : 0.f;
     const size_t row = (size_t)(row0 + m);
     DZ[m * kPolZS + n] = dz;
-    if (n < 192) g.dz_c2[(row * 3 + n % 3) * 64 + n / 3] = dz;
-    else if (n < 320) g.dz_in[2][row * 128 + n - 192] = dz;
-    else g.dz_ac[2][row * 128 + n - 320] = dz;
+    if (n < 192) g.dz[POL_L_C2][(row * 3 + n % 3) * 64 + n / 3] = dz;
+    else if (n < 320) g.dz[POL_L_IN2][row * 128 + n - 192] = dz;
+    else g.dz[POL_L_AC2][row * 128 + n - 320] = dz;
   });
   __syncthreads();
 
   // ---- the inertial and last_action MLPs: down to the first layer's dZ (their inputs need no gradient)
+  constexpr auto same = [](int a, int b) { return pol_layer(a, C).N == pol_layer(b, C).N && pol_layer(a, C).K == pol_layer(b, C).K; };
+  static_assert(same(POL_L_IN1, POL_L_AC1) && same(POL_L_IN2, POL_L_AC2), "the two chains' hidden layers have one shape");
 #pragma unroll
-  for (int chain = 0; chain < 2; ++chain) {
-    const int* w = chain ? P.ac_w : P.in_w;
-    float* const* dz = chain ? g.dz_ac : g.dz_in;
-    const int sv1 = chain ? POL_SV_AC1X : POL_SV_IN1X, sv2 = chain ? POL_SV_AC2X : POL_SV_IN2X;
-    pol_gemm<128, 128>(DZ + 192 + 128 * chain, kPolZS, pol_wT<128>(prm + w[2]), zero, [&](int m, int n, float v) {
+  for (int chain = 0; chain < 2; ++chain) {   // unrolled: l0, and with it every index into P and g, is a compile-time constant
+    const int l0 = chain ? POL_L_AC0 : POL_L_IN0;
+    const int sv1 = pol_layer(l0 + 1, C).x, sv2 = pol_layer(l0 + 2, C).x;
+    pol_linear_back<POL_L_IN2, C>(P, DZ + 192 + 128 * chain, kPolZS, [&](int m, int n, float v) {
       const float d = at(sv2, m, 0, n) > 0.f ? v : 0.f;
       T1[m * kPolTS + n] = d;
-      dz[1][(size_t)(row0 + m) * 128 + n] = d;
-    });
+      g.dz[l0 + 1][(size_t)(row0 + m) * 128 + n] = d;
+    }, l0 + 2);
     __syncthreads();
-    pol_gemm<128, 128>(T1, kPolTS, pol_wT<128>(prm + w[1]), zero, [&](int m, int n, float v) {
-      dz[0][(size_t)(row0 + m) * 128 + n] = at(sv1, m, 0, n) > 0.f ? v : 0.f;
-    });
+    pol_linear_back<POL_L_IN1, C>(P, T1, kPolTS, [&](int m, int n, float v) {
+      g.dz[l0][(size_t)(row0 + m) * 128 + n] = at(sv1, m, 0, n) > 0.f ? v : 0.f;
+    }, l0 + 1);
     __syncthreads();
   }
 
@@ -208,13 +218,52 @@ __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyPar
       T2[m * kPolTS + co] = DZ[m * kPolZS + co * 3 + ow2];
     }
     __syncthreads();
-    pol_gemm<64, 128>(T2, kPolTS, pol_wT<128>(prm + P.c2w), zero, [&](int m, int n, float v) {
+    pol_linear_back<POL_L_C2, C>(P, T2, kPolTS, [&](int m, int n, float v) {
       // n = ci * 4 + kh * 2 + kw: conv1 channel ci at position p = ow2 * 4 + kh * 2 + kw
       const float d = at(POL_SV_C2X, m, ow2, n) > 0.f ? v : 0.f;
-      g.dz_c1[((size_t)(row0 + m) * 12 + ow2 * 4 + (n & 3)) * 32 + (n >> 2)] = d;
+      g.dz[POL_L_C1][((size_t)(row0 + m) * 12 + ow2 * 4 + (n & 3)) * 32 + (n >> 2)] = d;
     });
     __syncthreads();
   }
+}
+
+// The workspace of te_policy_ppo_grad for n rows (Bp = n rounded up to the tile): every layer's input X [R][K] and pre-activation
+// gradient dZ [R][N] row-major, R = Bp x the layer's positions, then the split-K partials, in the order of the take() calls.  Host
+// only.  With ws == NULL only the size is computed; otherwise the tile kernel's pointers and the split-K plan are filled in.
+inline size_t policy_grad_layout(int C, int n, char* ws, const PolicyParams& P, float* grad, float* stats, GradTileArgs* ta, GradPlan* gp) {
+  const size_t Bp = ((size_t)n + kPolTileM - 1) / kPolTileM * kPolTileM;
+  size_t off = 0;
+  auto take = [&](size_t rows, int cols) {
+    float* at = ws ? reinterpret_cast<float*>(ws + off) : nullptr;
+    off += (rows * cols * sizeof(float) + 255) / 256 * 256;
+    return at;
+  };
+  GradTileArgs t{};
+  for (int l = 0; l < POL_L_WEIGHTS; ++l) { const PolLayer y = pol_layer(l, C); t.save_pos[y.x] = y.pos; t.save_ld[y.x] = y.K; }
+  for (int sv = 0; sv < POL_SV_COUNT; ++sv) t.save[sv] = take(Bp * t.save_pos[sv], t.save_ld[sv]);
+  for (int l = 0; l < POL_L_COUNT; ++l) t.dz[l] = take(Bp * pol_layer(l, C).pos, pol_layer(l, C).N);
+
+  GradPlan g{};
+  for (int l = 0; l < kGradLayers; ++l) {
+    const PolLayer y = pol_layer(l, C);
+    GradLayer& L = g.L[l];
+    L.dz = t.dz[l];
+    L.x = l < POL_L_WEIGHTS ? t.save[y.x] : nullptr;
+    L.N = y.N; L.K = y.K; L.R = (int)(Bp * y.pos);
+    L.ntiles = (y.N + kGradTile - 1) / kGradTile;
+    L.ktiles = (y.K + 1 + kGradTile - 1) / kGradTile;
+    L.slices = (L.R + kGradSlice - 1) / kGradSlice;
+    L.wg0 = g.wgs; L.word0 = g.words;
+    g.wgs += L.slices * L.ntiles * L.ktiles;
+    g.words += y.N * (y.K + 1);
+    L.part = take((size_t)L.slices * y.N, y.K + 1);
+    L.w_out = grad && l < POL_L_WEIGHTS ? grad + P.at[l].w : nullptr;
+    L.b_out = l == POL_L_STATS ? stats : (grad ? grad + (l == POL_L_LOGSTD ? P.log_std : P.at[l].b) : nullptr);
+    L.scale = l == POL_L_STATS ? 1.f / (float)n : 1.f;   // the statistics are means over the n rows
+  }
+  if (ta) *ta = t;
+  if (gp) *gp = g;
+  return off;
 }
 
 // The layer of work item `i` (workgroup or word): the table is indexed with compile-time indices only, so it stays in SGPRs.

@@ -94,6 +94,16 @@ def policy_param_words(lidar_channels: int) -> int:
     return int(out.value)
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def require_f32(who: str, name: str, t: torch.Tensor, shape, device: torch.device, shown: Optional[str] = None) -> None:
+    """Every float array of the policy's ABI calls: contiguous float32 of `shape` on `device` (`shown`: the shape as the message spells it)."""
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous float32 {shown or shape} tensor on {device}")
+
+
 class FusedPolicy:
     """Inference of a LidarInertialActionPolicy by te_policy_act: the forward pass, the Gaussian sample, its log-prob and the
     clamp of the action in one HIP launch.  The weights are packed into ONE device buffer that keeps its address for the life of
@@ -149,8 +159,7 @@ class FusedPolicy:
                 if name == "adv_mean_std":
                     continue
                 raise ValueError(f"FusedPolicy.ppo_grad: {name} is required")
-            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"FusedPolicy.ppo_grad: {name} must be a contiguous float32 {shape} tensor on {self.device}")
+            require_f32("FusedPolicy.ppo_grad", name, t, shape, self.device)
         if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != self.device or not index.is_contiguous()):
             raise ValueError(f"FusedPolicy.ppo_grad: index must be a contiguous 1-D int64 tensor on {self.device}")
         if b == 0:
@@ -165,12 +174,11 @@ class FusedPolicy:
                                    "call once with this minibatch size before capture")
             self._grad_ws = None           # free the old workspace before the larger one is allocated
             ws = self._grad_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(lib.te_policy_ppo_grad(self.params.data_ptr(), self.lidar_channels, b, ptr(index), lidar.data_ptr(), inertial.data_ptr(),
+            _lib.check(lib.te_policy_ppo_grad(self.params.data_ptr(), self.lidar_channels, b, _ptr(index), lidar.data_ptr(), inertial.data_ptr(),
                                               last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                              ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef), grad_out.data_ptr(),
+                                              _ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef), grad_out.data_ptr(),
                                               stats_out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "te_policy_ppo_grad")
 
     def _call(self, obs, eps, outs):
@@ -178,15 +186,12 @@ class FusedPolicy:
         n = lidar.shape[0]
         for name, t, shape in (("lidar", lidar, (n, self.lidar_channels, 13, 26)), ("inertial_data", inertial, (n, 15)),
                                ("last_action", last_action, (n, 4)), ("eps", eps, (n, 4))):
-            if t is None:
-                continue
-            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"FusedPolicy: {name} must be a contiguous float32 {shape} tensor on {self.device}")
-        ptr = lambda t: None if t is None else t.data_ptr()
+            if t is not None:
+                require_f32("FusedPolicy", name, t, shape, self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             _lib.check(_lib.load().te_policy_act(self.params.data_ptr(), self.lidar_channels, n, lidar.data_ptr(), inertial.data_ptr(),
-                                                 last_action.data_ptr(), ptr(eps), *(ptr(o) for o in outs), stream), "te_policy_act")
+                                                 last_action.data_ptr(), _ptr(eps), *(_ptr(o) for o in outs), stream), "te_policy_act")
 
     def forward(self, obs: Dict[str, torch.Tensor]):
         """(mu [N, 4], value [N]) of the module's forward."""

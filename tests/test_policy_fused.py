@@ -5,6 +5,7 @@ Tolerance: |d| <= 1e-4 + 1e-4 |ref| against the PyTorch module in fp32.  The ker
 it is not bit-exact; the measured gap over every parity case below is printed (pytest -s): on the MI355X the largest |d| was
 1.5e-7 on mu and 1.2e-7 on value, 0.1 % of the bound."""
 import ctypes as C
+import hashlib
 import os
 import re
 
@@ -33,7 +34,11 @@ def lib():
 def test_param_words(lib):
     from dronechase_amd.ppo import LidarInertialActionPolicy, policy_param_words
     assert policy_param_words(3) == 235049
-    assert policy_param_words(2) == 235049 - 512
+    assert policy_param_words(2) == 235049 - 512 == 234537
+    # from the layer shapes: conv1 32 * 16 C + 32, conv2 8 256, the inertial chain 35 072, the action chain 33 664, the trunk 114 944,
+    # two heads of 20 608, mu 260, value 65, log_std 4
+    for c in (2, 3):
+        assert policy_param_words(c) == (32 * 16 * c + 32) + 8256 + 35072 + 33664 + 114944 + 2 * 20608 + 260 + 65 + 4
     for c in (2, 3):
         p = LidarInertialActionPolicy(lidar_shape=(c, 13, 26))
         assert sum(x.numel() for x in p.parameters()) == policy_param_words(c)
@@ -151,6 +156,35 @@ def test_parity_with_the_module(c):
             _check(torch, mu, mu_ref, "mu"); _check(torch, v, v_ref, "value")
     print(f"\nlidar_channels={c}: largest |d| so far: mu {MARGIN['mu'][0]:.2e}, value {MARGIN['value'][0]:.2e}; "
           f"largest fraction of the bound: mu {MARGIN['mu'][1]:.3f}, value {MARGIN['value'][1]:.3f}")
+
+
+# SHA-256 of mu | value | action | logp | action_env of the call below, recorded from the library of commit 66a9492 on the MI355X:
+# the kernel is bitwise deterministic for fixed inputs, so a refactor of the policy's description leaves these as they are
+ACT_DIGEST = {2: "c65548f19cb5066403dce312d88165d7466a647245979699cef1607c3d57e068",
+              3: "19215395f089bdf7311d472effa4f7e15abdde3eb5b38c24ffc96ea79bdf1aa4"}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", [2, 3])
+def test_act_is_bitwise_the_recorded_one(lib, c):
+    """n = 33: two tiles, the second with one live row and 31 padding rows.  Every input comes from numpy's PCG64, through the raw ABI."""
+    torch = _gpu()
+    n = 33
+    rng = np.random.default_rng(1000 + c)
+    u = lambda lo, hi, *s: torch.from_numpy(rng.uniform(lo, hi, s).astype(np.float32)).to("cuda:0")
+    words = C.c_size_t()
+    assert lib.te_policy_param_words(c, C.byref(words)) == 0
+    params = u(-0.1, 0.1, words.value)
+    lidar, inertial, last_action, eps = u(0, 1, n, c, 13, 26), u(-1, 1, n, 15), u(-1, 1, n, 4), u(-2, 2, n, 4)
+    outs = [torch.full(s, float("nan"), device="cuda:0") for s in ((n, 4), (n,), (n, 4), (n,), (n, 4))]   # mu value action logp action_env
+    rc = lib.te_policy_act(params.data_ptr(), c, n, lidar.data_ptr(), inertial.data_ptr(), last_action.data_ptr(), eps.data_ptr(),
+                           *[t.data_ptr() for t in outs], torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.te_last_error()
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(t).all()) for t in outs)
+    digest = hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in outs)).hexdigest()
+    print(f"\nte_policy_act C={c}: {digest}")
+    assert digest == ACT_DIGEST[c]
 
 
 @pytest.mark.gpu

@@ -8,6 +8,7 @@ dL/dY then enters the bias sum or not.  Measured on the MI355X (trained weights,
 moved inertial.4.bias by 1.78e-6 = its row's dL/dY exactly, while fp32 autograd was within 1.3e-10 of fp64 there.  The measured gaps
 are printed (pytest -s)."""
 import ctypes as C
+import hashlib
 import os
 import re
 
@@ -52,6 +53,18 @@ def test_workspace_bytes_monotone(lib):
                       (3, (1 << 27) + 1, b"at most")):
         assert lib.te_policy_grad_workspace_bytes(c, n, C.byref(out)) != 0 and msg in lib.te_last_error(), (c, n)
     assert lib.te_policy_grad_workspace_bytes(3, 8, None) != 0 and b"null" in lib.te_last_error()
+
+
+# te_policy_grad_workspace_bytes of commit 66a9492 (its library built and called on the host: the function touches no device); the
+# order and the sizes of the workspace's buffers are part of what a caller's allocation relies on
+WS_ROWS = (1, 32, 33, 161, 2048, 2049, 65536)
+WS_BYTES = {2: (1467904, 1467904, 1996032, 4113664, 34868224, 36335104, 1115752192),
+            3: (1494528, 1494528, 2047232, 4265216, 36465664, 37959168, 1166870272)}
+
+
+def test_workspace_bytes_are_the_recorded_ones(lib):
+    for c in (2, 3):
+        assert tuple(_ws_bytes(lib, c, n) for n in WS_ROWS) == WS_BYTES[c]
 
 
 def test_bad_arguments_fail_through_last_error(lib):
@@ -221,6 +234,43 @@ def test_gradient_parity_with_autograd(c):
             if obs["lidar"].shape[0] > 1000 and idx is None:      # both clip branches were taken
                 assert 0.1 < float(stats[3]) < 0.9, (tag, stats.tolist())
     print(f"\nlidar_channels={c}: largest |d| as a fraction of the bound so far: gradient {GAP['grad']:.3f}, statistics {GAP['stats']:.3f}")
+
+
+# SHA-256 of (grad, stats) of the call below, recorded from the library of commit 66a9492 on the MI355X: every sum of the three
+# kernels has a fixed order, so a refactor of the policy's description leaves these as they are
+GRAD_DIGEST = {2: ("cb716a9248cff5e8911b3db8fb4e2ac8a2a220668657dfb73c923b24141e1248", "f36b37cf0a0e37c99eccf9f8a1a3e1900b2079949ef92b5636e22646021b6eee"),
+               3: ("306c66bf3ebd710d914de046a77425eb19b9541cc3f8d6ec5357455dfd0839f0", "97e51954084fa257cfb3d0f54cf3f7af4e5d22387da3ffc5cb20940e456b6ca6")}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", [2, 3])
+def test_ppo_grad_is_bitwise_the_recorded_one(lib, c):
+    """2 049 rows picked by a permuted index out of 2 100: Bp = 2 080, so every layer's reduction crosses a kGradSlice = 2 048 boundary
+    (conv1 has 13 slices) and the last tile has one live row.  Every input comes from numpy's PCG64, through the raw ABI."""
+    torch = _gpu()
+    n, m = 2049, 2100
+    rng = np.random.default_rng(2000 + c)
+    u = lambda lo, hi, *s: torch.from_numpy(rng.uniform(lo, hi, s).astype(np.float32)).to("cuda:0")
+    words = C.c_size_t()
+    assert lib.te_policy_param_words(c, C.byref(words)) == 0
+    params = u(-0.1, 0.1, words.value)
+    lidar, inertial, last_action = u(0, 1, m, c, 13, 26), u(-1, 1, m, 15), u(-1, 1, m, 4)
+    action, old_logp, adv, ret = u(-1, 1, m, 4), u(-5, -3.5, m), u(-2, 2, m), u(-1, 1, m)
+    index = torch.from_numpy(rng.permutation(m)[:n].astype(np.int64)).to("cuda:0")
+    ms = torch.tensor([0.1, 1.3], device="cuda:0")
+    grad = torch.full((words.value,), float("nan"), device="cuda:0")
+    stats = torch.full((4,), float("nan"), device="cuda:0")
+    ws = torch.empty(_ws_bytes(lib, c, n), dtype=torch.uint8, device="cuda:0")
+    rc = lib.te_policy_ppo_grad(params.data_ptr(), c, n, index.data_ptr(), lidar.data_ptr(), inertial.data_ptr(), last_action.data_ptr(),
+                                action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(), ms.data_ptr(), 0.2, 0.5, 0.01,
+                                grad.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, lib.te_last_error()
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(grad).all()) and bool(torch.isfinite(stats).all())
+    assert 0.0 < float(stats[3]) < 1.0        # both sides of the clip were taken
+    digests = tuple(hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest() for t in (grad, stats))
+    print(f"\nte_policy_ppo_grad C={c}: {digests}")
+    assert digests == GRAD_DIGEST[c]
 
 
 @pytest.mark.gpu
