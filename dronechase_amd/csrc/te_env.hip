@@ -15,10 +15,11 @@
 //                            spawn phase, one (env, slot) per thread -> observation rows + the allies' commands
 //                            and the flight plan of the next step -> patch the hit cells into the background.
 // (te_step_stacked adds stacked_kernel, te_stacked.hpp; exp05 brackets te_step with te_observe_ally /
-// te_set_ally_actions, or with te_drive_wingman when a packed policy flies the ally.)
+// te_set_ally_actions, or with te_drive_wingman when a packed policy flies the ally: the kernels of a caller-driven
+// pursuer are te_wingman.hpp's.)
 // No MFMA: this is element-wise physics and byte streaming.  The MFMA kernels of the library are the policy's
-// inference, te_policy_act (te_policy.hpp) and te_drive_wingman's policy_drive_kernel, and its PPO gradient, te_policy_ppo_grad
-// (te_policy_grad.hpp); none is part of te_step.
+// inference, te_policy_act (te_policy.hpp) and te_drive_wingman's policy_drive_kernel (te_wingman.hpp), and its PPO gradient,
+// te_policy_ppo_grad (te_policy_grad.hpp); none is part of te_step.
 //
 // Reference citations are file:line under the reference's src/ tree.
 #include <hip/hip_runtime.h>
@@ -41,6 +42,7 @@
 #include "te_engage.hpp"
 #include "te_engage_slots.hpp"
 #include "te_policy.hpp"
+#include "te_wingman.hpp"
 #include "te_policy_grad.hpp"
 #include "te_monitor.hpp"
 
@@ -73,12 +75,8 @@ constexpr long long kHelpMaxPairs = 98304;
 #else
 #define TE_K1_ATTR
 #endif
-// Background job of one launch: the fill waves cover the whole buffer, grid-stride.
-// the background is written once and not read by this launch: non-temporal ("nt") stores keep it from displacing the
-// drone state in L2 (measured 58.7 -> 56.1 us per launch)
-typedef float te_f4 __attribute__((ext_vector_type(4)));
+// Background job of one launch: the fill waves cover the whole buffer, grid-stride (TE_FILL_STORE, te_device.hpp).
 typedef uint32_t te_u4 __attribute__((ext_vector_type(4)));
-#define TE_FILL_STORE(ptr) __builtin_nontemporal_store((te_f4){1.0f, 1.0f, 1.0f, 1.0f}, reinterpret_cast<te_f4*>(ptr))
 // mode 0 / 1: stream ones over the whole buffer (pointer loop for buffers beyond the buffer descriptor's reach / scalar buffer loop).  mode 3 (persistent observation,
 // te_set_persistent_obs): the buffer still holds the previous observation; wave w = list * nchunks + chunk sets the cells that observation
 // patched in output sphere `list` (= observer * 6 + sphere) of the chunk's 64 envs back to one — scattered stores that ride on the flights
@@ -696,194 +694,6 @@ __global__ __launch_bounds__(256) void fill_ones_kernel(float* __restrict__ dst,
   for (size_t i = (quads << 2) + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_floats; i += stride) dst[i] = 1.0f;
 }
 
-// exp05: Exp05_vFinal_Task.compute_lw_observation (exp05_vFinal_task.py:265-292) of pursuer `me` = 1.  One workgroup per
-// chunk of 64 envs, straight from the state planes (coalesced over envs): (env, drone) items compute the LIDAR cell and
-// range of every other armed drone seen from the ally's IMU attitude into LDS, all threads stream the chunk's tile
-// (ones), then the owner of each cell is patched in.  Same rules as the agent's sphere: closer wins in slot order, empty
-// right after a reset.
-__global__ __launch_bounds__(256) void observe_ally_kernel(Params p, int me, float* __restrict__ lidar, float* __restrict__ inertial,
-                                                           float* __restrict__ last_action, uint8_t* __restrict__ active) {
-  __shared__ uint32_t s_cell[kMaxD * kEPB];
-  __shared__ float s_rhat[kMaxD * kEPB];
-  const te_config& c = p.cfg;
-  const int D = p.D;
-  const int env0 = blockIdx.x * kEPB, nvalid = min(kEPB, p.N - env0);
-  const int l = threadIdx.x & (kEPB - 1), w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const bool valid = l < nvalid;
-  const GView v{p.dstate, p.estate, D, p.Npad, env0 + l, c.n_pursuers};   // planes are padded to Npad: in bounds for every lane
-  const int step = v.egi(TE_E_STEP);
-  const bool sees = lidar && valid && step != 0;
-  // wave roles: the last wave only streams the tile (a wave that has stores in flight waits for them before any later
-  // load returns: in-order vmcnt), the others compute the features meanwhile
-  const int nfeat = nw - 1;
-  if (sees && w < nfeat) {
-    const Q4 q = quat_of_euler(V3{v.gf(TE_D_OBS_EULER, me), v.gf(TE_D_OBS_EULER + 1, me), v.gf(TE_D_OBS_EULER + 2, me)});
-    const float n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
-    const M3 R = rotation(Q4{-q.x / n2, -q.y / n2, -q.z / n2, q.w / n2});
-    const V3 own = obs_pos(v, me);
-    for (int j = w; j < D; j += nfeat) {
-      uint32_t cell = 0xFFFFFFFFu; float rhat = 1.0f;
-      if (j != me && v.gi(TE_D_ARMED, j)) { int cj; lidar_cell(c, mul(R, sub(obs_pos(v, j), own)), cj, rhat); cell = (uint32_t)cj; }
-      s_cell[j * kEPB + l] = cell; s_rhat[j * kEPB + l] = rhat;
-    }
-  }
-  if (lidar && w == nfeat) {  // the chunk's tile: 64 * 1014 floats, 16-byte aligned; non-temporal like the sub-step kernel's background
-    float* tile = lidar + (size_t)env0 * lidar_words(c);
-    const int total = nvalid * lidar_words(c), quads = total >> 2;
-    for (int qi = l; qi < quads; qi += kEPB) TE_FILL_STORE(reinterpret_cast<float4*>(tile) + qi);
-    for (int f = (quads << 2) + l; f < total; f += kEPB) tile[f] = 1.0f;
-  }
-  if (w == 0 && valid) {
-    const int env = env0 + l;
-    if (active) active[env] = v.gi(TE_D_ARMED, me) ? 1 : 0;
-    if (last_action)
-      reinterpret_cast<float4*>(last_action)[env] = make_float4(v.gf(TE_D_ALLY_ACTION, me), v.gf(TE_D_ALLY_ACTION + 1, me),
-                                                                 v.gf(TE_D_ALLY_ACTION + 2, me), v.gf(TE_D_ALLY_ACTION + 3, me));
-    if (inertial) {
-      float in[TE_OBS_INERTIAL_WORDS];
-      inertial_obs(c, v, step, in, me);
-#pragma unroll
-      for (int k = 0; k < TE_OBS_INERTIAL_WORDS; ++k) inertial[(size_t)env * TE_OBS_INERTIAL_WORDS + k] = in[k];
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the ones must have landed before any patch
-  __syncthreads();
-  if (!sees) return;
-  // owner of a cell = smallest range, the earlier slot on ties (strict '<' in slot order, lidar_math.py:262-311); a
-  // feature clipped to 1.0 never enters an empty cell
-  float* base = lidar + (size_t)(env0 + l) * lidar_words(c);
-  for (int j = w; j < D; j += nw) {
-    const uint32_t cell = s_cell[j * kEPB + l];
-    const float rhat = s_rhat[j * kEPB + l];
-    if (cell == 0xFFFFFFFFu || !(rhat < 1.0f)) continue;
-    bool owner = true;
-    for (int k = 0; k < D; ++k) {
-      if (k == j || s_cell[k * kEPB + l] != cell) continue;
-      const float rk = s_rhat[k * kEPB + l];
-      if (rk < rhat || (rk == rhat && k < j)) owner = false;
-    }
-    if (!owner) continue;
-    base[cell] = rhat;
-    base[TE_LIDAR_CELLS + cell] = (float)(j < c.n_pursuers ? TE_TYPE_LOYALWINGMAN : TE_TYPE_LOITERINGMUNITION) / 5.0f;
-    if (c.lidar_channels != 2) base[2 * TE_LIDAR_CELLS + cell] = 0.1f;
-  }
-}
-// The same observation as two launches for full-size batches (48 us instead of 64 at 65 536 envs):
-//   ally_view_kernel   single-wave workgroups: `n_fill` of them stream the background in the sub-step kernel's fill-wave
-//                      shape while one wave per chunk (lane = env) computes cells / ranges / owners and leaves them as
-//                      (cell | type << 16, r_hat) planes in a scratch buffer, and writes the inertial / last-action rows;
-//   ally_patch_kernel  one thread per (env, drone): the owners' three floats into the finished background.
-__global__ __launch_bounds__(64) void ally_view_kernel(Params p, int me, float* __restrict__ lidar, uint32_t quads, uint32_t n_fill,
-                                                       float* __restrict__ inertial, float* __restrict__ last_action,
-                                                       uint8_t* __restrict__ active, uint32_t* __restrict__ scratch) {
-  __shared__ uint32_t s_cell[kMaxD * kEPB];
-  __shared__ float s_rhat[kMaxD * kEPB];
-  const int l = threadIdx.x;
-  if (blockIdx.x < n_fill) {
-    const uint32_t stride = n_fill * 64u;
-    for (uint32_t q = blockIdx.x * 64u + (uint32_t)l; q < quads; q += stride) TE_FILL_STORE(reinterpret_cast<float4*>(lidar) + q);
-    return;
-  }
-  const te_config& c = p.cfg;
-  const int D = p.D;
-  const int env = (int)(blockIdx.x - n_fill) * kEPB + l;
-  const bool valid = env < p.N;
-  const GView v{p.dstate, p.estate, D, p.Npad, env, c.n_pursuers};   // planes are padded to Npad: in bounds for every lane
-  const int step = v.egi(TE_E_STEP);
-  const bool sees = valid && step != 0;
-  if (sees) {
-    const Q4 q = quat_of_euler(V3{v.gf(TE_D_OBS_EULER, me), v.gf(TE_D_OBS_EULER + 1, me), v.gf(TE_D_OBS_EULER + 2, me)});
-    const float n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
-    const M3 R = rotation(Q4{-q.x / n2, -q.y / n2, -q.z / n2, q.w / n2});
-    const V3 own = obs_pos(v, me);
-    for (int j = 0; j < D; ++j) {
-      uint32_t cell = 0xFFFFFFFFu; float rhat = 1.0f;
-      if (j != me && v.gi(TE_D_ARMED, j)) { int cj; lidar_cell(c, mul(R, sub(obs_pos(v, j), own)), cj, rhat); cell = (uint32_t)cj; }
-      s_cell[j * kEPB + l] = cell; s_rhat[j * kEPB + l] = rhat;
-    }
-  }
-  if (valid) {
-    if (active) active[env] = v.gi(TE_D_ARMED, me) ? 1 : 0;
-    if (last_action)
-      reinterpret_cast<float4*>(last_action)[env] = make_float4(v.gf(TE_D_ALLY_ACTION, me), v.gf(TE_D_ALLY_ACTION + 1, me),
-                                                                 v.gf(TE_D_ALLY_ACTION + 2, me), v.gf(TE_D_ALLY_ACTION + 3, me));
-    if (inertial) {
-      float in[TE_OBS_INERTIAL_WORDS];
-      inertial_obs(c, v, step, in, me);
-#pragma unroll
-      for (int k = 0; k < TE_OBS_INERTIAL_WORDS; ++k) inertial[(size_t)env * TE_OBS_INERTIAL_WORDS + k] = in[k];
-    }
-  }
-  // owner of a cell = smallest range, the earlier slot on ties; a feature clipped to 1.0 never enters an empty cell
-  // (each lane reads back only what it wrote: no barrier)
-  for (int j = 0; j < D; ++j) {
-    uint32_t out = 0xFFFFFFFFu; float rh = 1.0f;
-    if (sees) {
-      const uint32_t cell = s_cell[j * kEPB + l];
-      const float rhat = s_rhat[j * kEPB + l];
-      if (cell != 0xFFFFFFFFu && rhat < 1.0f) {
-        bool owner = true;
-        for (int k = 0; k < D; ++k) {
-          if (k == j || s_cell[k * kEPB + l] != cell) continue;
-          const float rk = s_rhat[k * kEPB + l];
-          if (rk < rhat || (rk == rhat && k < j)) owner = false;
-        }
-        if (owner) { out = cell | ((uint32_t)(j < c.n_pursuers ? TE_TYPE_LOYALWINGMAN : TE_TYPE_LOITERINGMUNITION) << 16); rh = rhat; }
-      }
-    }
-    scratch[(size_t)(2 * j) * p.Npad + env] = out; scratch[(size_t)(2 * j + 1) * p.Npad + env] = __float_as_uint(rh);
-  }
-}
-__global__ __launch_bounds__(256) void ally_patch_kernel(Params p, float* __restrict__ lidar, const uint32_t* __restrict__ scratch) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)p.D * p.Npad) return;
-  const int j = (int)(i / p.Npad), env = (int)(i - (size_t)j * p.Npad);
-  if (env >= p.N) return;
-  const uint32_t w = scratch[(size_t)(2 * j) * p.Npad + env];
-  if (w == 0xFFFFFFFFu) return;
-  float* d = lidar + (size_t)env * lidar_words(p.cfg) + (w & 0xFFFFu);
-  d[0] = __uint_as_float(scratch[(size_t)(2 * j + 1) * p.Npad + env]); d[TE_LIDAR_CELLS] = (float)(w >> 16) / 5.0f;
-  if (p.cfg.lidar_channels != 2) d[2 * TE_LIDAR_CELLS] = 0.1f;
-}
-// exp05: pursuer.drive(action) of drive_lw_rl_agent (exp05_vFinal_task.py:255-260; quadcopter.py:379-413) for an armed pursuer
-// `me` of env v: the velocity command, the set-point, and the action remembered as the pursuer's last action.
-TE_DEV void drive_caller_pursuer(const GView& v, int me, float4 a) {
-  float vx, vy, vz;
-  command_to_velocity(a.x, a.y, a.z, a.w, vx, vy, vz);
-  v.sf(TE_X_CMD + 0, me, vx); v.sf(TE_X_CMD + 1, me, vy); v.sf(TE_X_CMD + 2, me, vz);
-  v.sf(TE_D_SETPOINT + 0, me, vx); v.sf(TE_D_SETPOINT + 1, me, vy); v.sf(TE_D_SETPOINT + 2, me, 0.0f); v.sf(TE_D_SETPOINT + 3, me, vz);
-  v.sf(TE_D_ALLY_ACTION + 0, me, a.x); v.sf(TE_D_ALLY_ACTION + 1, me, a.y); v.sf(TE_D_ALLY_ACTION + 2, me, a.z); v.sf(TE_D_ALLY_ACTION + 3, me, a.w);
-}
-
-__global__ __launch_bounds__(256) void set_ally_actions_kernel(Params p, int me, const float* __restrict__ actions) {
-  const int env = blockIdx.x * 256 + threadIdx.x;
-  if (env >= p.N) return;
-  const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
-  if (!v.gi(TE_D_ARMED, me)) return;
-  drive_caller_pursuer(v, me, reinterpret_cast<const float4*>(actions)[env]);
-}
-
-// te_drive_wingman: the deterministic predict of the packed policy on pursuer `me`'s observation (te_observe_wingman's output,
-// read as te_policy_act reads its rows), then set_ally_actions_kernel's drive with the clamped mean.  pol_forward is the one
-// policy_act_kernel runs, so mu is bitwise te_policy_act's.  Every row is computed; rows of envs whose pursuer is dead keep
-// their state (the reference does not call predict for them), mu is written for all rows.
-template <int C>
-__global__ __launch_bounds__(kPolThreads) void policy_drive_kernel(PolicyParams P, PolicyIn in, Params p, int me, float* __restrict__ mu) {
-  extern __shared__ __attribute__((aligned(16))) float pol_lds[];
-  const int tid = threadIdx.x, env = blockIdx.x * kPolTileM + tid;
-  pol_forward<C>(P, in, pol_lds, blockIdx.x * kPolTileM, PolNoSave{});
-  if (tid >= kPolTileM || env >= in.n) return;
-  const float* MU = pol_mu_lds(pol_lds) + tid * 4;   // read back by the thread that computed it
-  if (mu) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) mu[(size_t)env * 4 + a] = MU[a];
-  }
-  const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
-  if (!v.gi(TE_D_ARMED, me)) return;
-  drive_caller_pursuer(v, me, make_float4(fmaxf(fminf(MU[0], 1.f), -1.f), fmaxf(fminf(MU[1], 1.f), -1.f), fmaxf(fminf(MU[2], 1.f), -1.f),
-                                          fmaxf(fminf(MU[3], 1.f), 0.f)));
-}
-
 // te_observe: current observation without stepping
 __global__ __launch_bounds__(256) void observe_kernel(Params p, ObsOut o) {
   extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
@@ -971,6 +781,12 @@ struct KernelPlan {
   Launch<StackParams> ring_push;                        // stacked observation: pushes the step's ring entries (none: stacked_kernel does)
   Launch<StackParams, StackOut> stack_view;             // stacked observation: stack_view_kernel or stacked_kernel
   size_t observe_lds = 0;                               // observe_kernel
+  // te_observe_wingman (te_wingman.hpp), set for configs with a caller-driven pursuer only.  wingman_one serves shards below 4 096 envs
+  // and any call without a LIDAR buffer; wingman_view + wingman_patch, when set, serve a full call and need the scratch planes.
+  Launch<Params, int, float*, float*, float*, uint8_t*> wingman_one;                                      // observe_ally_kernel
+  Launch<Params, int, float*, uint32_t, uint32_t, float*, float*, uint8_t*, uint32_t*> wingman_view;   // ally_view_kernel
+  Launch<Params, float*, const uint32_t*> wingman_patch;                                                 // ally_patch_kernel
+  uint32_t wingman_fill_waves = 256;   // background waves of ally_view_kernel: one per CU of an MI355X
   bool records_cells = false;   // the kernel that patches the LIDAR observation records the cells (te_set_persistent_obs); the LDS fallbacks do not
   int n_fill_waves = 256, dense_min = kDenseMin;
 };
@@ -1131,6 +947,15 @@ static const char* plan_kernels(const te_config& c, KernelPlan* out, size_t mult
     else k.stack_view = {TE_KERNEL(stacked_kernel), kStackThreads, (size_t)stack_lds_rows(D, P) * kEPB * sizeof(uint32_t)};
     k.records_cells = dm != 0;
   }
+  // ---- the caller-driven pursuer's observation: two launches for full-size shards whose background is whole 16-byte quads within 32 bits
+  if (c.ally_policy == TE_ALLY_EXTERNAL || ((uint32_t)c.evaluation >> 8) != 0u) {
+    const size_t n_floats = (size_t)c.n_envs * lidar_words(c);
+    k.wingman_one = {TE_KERNEL(observe_ally_kernel), 256, 0};
+    if (c.n_envs >= 4096 && (n_floats & 3) == 0 && (n_floats >> 2) < (1ull << 32)) {
+      k.wingman_view = {TE_KERNEL(ally_view_kernel), 64, 0};
+      k.wingman_patch = {TE_KERNEL(ally_patch_kernel), 256, 0};
+    }
+  }
   return nullptr;
 }
 
@@ -1141,7 +966,7 @@ struct te_env {
   KernelPlan k;                // the kernels it launches (plan_kernels)
   size_t dbg_words = 0;       // diagnostic builds: length of p.dbg
   float* zero_actions = nullptr;     // te_step_students: the [N,4] action batch nobody reads (every pursuer is scripted)
-  uint32_t* ally_scratch = nullptr;  // te_observe_wingman: owner planes between its two launches (te_create allocates them when a wingman is caller-driven)
+  uint32_t* ally_scratch = nullptr;  // te_observe_wingman: owner planes between its two launches (te_create allocates them when the plan has the two-launch form)
   // cfg.io_location == TE_IO_HOST: device staging of every I/O buffer of te_step / te_observe / te_reset / te_random_actions /
   // te_get_state / te_set_state (one allocation, carved at 256-byte boundaries by te_create)
   struct HostStage {
@@ -1293,9 +1118,9 @@ __attribute__((visibility("default"))) int te_create(const te_config* cfg, int32
         hipMemcpy(e->p.stage_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
       return bail("te_create: hipMalloc failed");
   }
-  // caller-driven wingmen (exp05's ally, Evaluation_Task's "nn" drivers): te_observe_wingman's scratch planes are allocated
-  // HERE, not on first use: the entry point only enqueues work (it must be legal under stream capture and never synchronise)
-  if (cfg->ally_policy == TE_ALLY_EXTERNAL || ((uint32_t)cfg->evaluation >> 8) != 0u) {
+  // caller-driven wingmen (exp05's ally, Evaluation_Task's "nn" drivers): the scratch planes of te_observe_wingman's two-launch form
+  // are allocated HERE, not on first use: the entry point only enqueues work (it must be legal under stream capture and never synchronise)
+  if (e->k.wingman_view.fn) {
     if (hipMalloc(&e->ally_scratch, (size_t)2 * D * e->p.Npad * 4) != hipSuccess) return bail("te_create: hipMalloc failed");
   }
   if (cfg->io_location == TE_IO_HOST) {
@@ -1352,6 +1177,8 @@ __attribute__((visibility("default"))) int te_kernel_plan(const te_config* cfg, 
   if (why || (why = plan_kernels(*cfg, &k))) return fail(why);
   std::string s = std::string("substeps=") + k.substeps[1].name + "\nsubsteps_nofill=" + k.substeps[0].name + "\nengage=" + k.engage.name + "\n" +
                   (k.ring_push.fn ? std::string("ring_push=") + k.ring_push.name + "\n" : "") + (k.stack_view.fn ? std::string("stack_view=") + k.stack_view.name + "\n" : "");
+  if (k.wingman_view.fn) s += std::string("wingman_view=") + k.wingman_view.name + "+" + k.wingman_patch.name + "\n";
+  else if (k.wingman_one.fn) s += std::string("wingman_view=") + k.wingman_one.name + "\n";
   if (s.size() >= out_bytes) return fail("te_kernel_plan: out_bytes too small (" + std::to_string(s.size() + 1) + " needed)");
   memcpy(out, s.c_str(), s.size() + 1);
   return 0;
@@ -1393,16 +1220,6 @@ __attribute__((visibility("default"))) int te_reset(te_env* e, const uint8_t* en
   return 0;
 }
 
-// Evaluation_Task.compute_info (evaluation_task.py:553-574): (lw_kills, lw_alive, lw_munitions, current_wave, step) per pursuer
-__global__ __launch_bounds__(256) void wingman_info_kernel(Params p, int32_t* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x, P = p.cfg.n_pursuers;
-  if (i >= p.N * P) return;
-  const int env = i / P, s = i - env * P;
-  const GView v{p.dstate, p.estate, p.D, p.Npad, env, P};
-  int32_t* row = out + (size_t)i * 5;
-  row[0] = v.gi(TE_D_KILLS, s); row[1] = v.gi(TE_D_ARMED, s) ? 1 : 0; row[2] = v.gi(TE_D_MUNITION, s);
-  row[3] = v.egi(TE_E_INFO_WAVE); row[4] = v.egi(TE_E_STEP);
-}
 __attribute__((visibility("default"))) int te_wingman_info(te_env* e, int32_t* wingman_info, void* stream) {
   if (!e || !wingman_info) return fail("te_wingman_info: null argument");
   if (!e->p.cfg.evaluation) return fail("te_wingman_info: per-wingman kills are only counted under cfg.evaluation (Evaluation_Task)");
@@ -1428,15 +1245,16 @@ __attribute__((visibility("default"))) int te_observe_wingman(te_env* e, int32_t
     return fail("te_observe_wingman: lidar and last_action must be 16-byte aligned");
   DeviceGuard guard(e->device);
   hipStream_t st = (hipStream_t)stream;
-  const size_t n_floats = (size_t)e->p.N * lidar_words(e->p.cfg);
-  const int nchunks = e->p.Npad / kEPB;
-  if (ally_lidar && (n_floats & 3) == 0 && (n_floats >> 2) < (1ull << 32) && e->p.N >= 4096) {  // full-size batches: two launches
+  const KernelPlan& k = e->k;
+  const unsigned nchunks = (unsigned)(e->p.Npad / kEPB);
+  if (ally_lidar && k.wingman_view.fn) {  // full-size shards: two launches
     if (!e->ally_scratch) return fail("te_observe_wingman: internal error: no scratch planes (te_create allocates them for caller-driven wingmen)");
-    hipLaunchKernelGGL(ally_view_kernel, dim3(256 + nchunks), dim3(64), 0, st, e->p, (int)wingman, ally_lidar, (uint32_t)(n_floats >> 2), 256u,
-                       ally_inertial, ally_last_action, ally_active, e->ally_scratch);
-    hipLaunchKernelGGL(ally_patch_kernel, dim3((unsigned)(((size_t)e->p.D * e->p.Npad + 255) / 256)), dim3(256), 0, st, e->p, ally_lidar, e->ally_scratch);
+    const size_t quads = (size_t)e->p.N * lidar_words(e->p.cfg) >> 2;
+    launch(k.wingman_view, k.wingman_fill_waves + nchunks, st, nullptr, nullptr, e->p, (int)wingman, ally_lidar, (uint32_t)quads, k.wingman_fill_waves,
+           ally_inertial, ally_last_action, ally_active, e->ally_scratch);
+    launch(k.wingman_patch, (unsigned)(((size_t)e->p.D * e->p.Npad + 255) / 256), st, nullptr, nullptr, e->p, ally_lidar, e->ally_scratch);
   } else {
-    hipLaunchKernelGGL(observe_ally_kernel, dim3(nchunks), dim3(256), 0, st, e->p, (int)wingman, ally_lidar, ally_inertial, ally_last_action, ally_active);
+    launch(k.wingman_one, nchunks, st, nullptr, nullptr, e->p, (int)wingman, ally_lidar, ally_inertial, ally_last_action, ally_active);
   }
   TE_HIP(hipGetLastError());
   return 0;
@@ -1672,10 +1490,7 @@ __global__ __launch_bounds__(256) void students_rows_kernel(Params p, const uint
   const int s = i / p.N, env = i - s * p.N;   // slot-major: consecutive threads = consecutive envs of one plane
   const GView v{p.dstate, p.estate, p.D, p.Npad, env, P};
   const size_t row = (size_t)env * P + s;
-  float in[TE_OBS_INERTIAL_WORDS];
-  inertial_obs(p.cfg, v, v.egi(TE_E_STEP), in, s);
-#pragma unroll
-  for (int k = 0; k < TE_OBS_INERTIAL_WORDS; ++k) inertial[row * TE_OBS_INERTIAL_WORDS + k] = in[k];
+  inertial_obs_row(p.cfg, v, v.egi(TE_E_STEP), s, inertial + row * TE_OBS_INERTIAL_WORDS);
   const bool armed = v.gi(TE_D_ARMED, s) != 0;
   const bool fresh = done[env] != 0 && p.cfg.auto_reset;   // the reset observation: nobody has been commanded yet
   float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -1709,12 +1524,7 @@ __global__ __launch_bounds__(256) void agent_rows_kernel(Params p, float* __rest
   const int env = blockIdx.x * 256 + threadIdx.x;
   if (env >= p.N) return;
   const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
-  if (inertial) {
-    float in[TE_OBS_INERTIAL_WORDS];
-    inertial_obs(p.cfg, v, v.egi(TE_E_STEP), in, 0);
-#pragma unroll
-    for (int k = 0; k < TE_OBS_INERTIAL_WORDS; ++k) inertial[(size_t)env * TE_OBS_INERTIAL_WORDS + k] = in[k];
-  }
+  if (inertial) inertial_obs_row(p.cfg, v, v.egi(TE_E_STEP), 0, inertial + (size_t)env * TE_OBS_INERTIAL_WORDS);
   if (last_action)
     reinterpret_cast<float4*>(last_action)[env] = make_float4(v.egf(TE_E_LAST_ACTION), v.egf(TE_E_LAST_ACTION + 1), v.egf(TE_E_LAST_ACTION + 2), v.egf(TE_E_LAST_ACTION + 3));
 }

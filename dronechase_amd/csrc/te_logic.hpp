@@ -632,6 +632,13 @@ template <class V> TE_DEV void inertial_obs(const te_config& c, const V& v, int 
   gun_state(c, v.gi(TE_D_MUNITION, s), v.gi(TE_D_LAST_FIRED, s), step, max_munition_of(c, s), g);
   out[12] = g[0]; out[13] = g[1]; out[14] = g[2];
 }
+// ... of drone s, straight into its row of an [rows, TE_OBS_INERTIAL_WORDS] output
+template <class V> TE_DEV void inertial_obs_row(const te_config& c, const V& v, int step, int s, float* __restrict__ row) {
+  float in[TE_OBS_INERTIAL_WORDS];
+  inertial_obs(c, v, step, in, s);
+#pragma unroll
+  for (int k = 0; k < TE_OBS_INERTIAL_WORDS; ++k) row[k] = in[k];
+}
 TE_DEV void write_obs_rows(const ObsOut& o, int env, const float inertial[TE_OBS_INERTIAL_WORDS], const float la[4]) {
   if (o.inertial) {
 #pragma unroll

@@ -155,3 +155,42 @@ def test_exp05_vecenv_driver_and_single_env_surface():
     o, r, term, trunc, info = e.step(np.array([0, 0, 1, 0.5], np.float32))
     assert o["lidar"].shape == (3, 13, 26) and trunc is False and set(info) >= {"agent_kills", "allies_kills", "deads", "current_wave"}
     e.close()
+
+
+@pytest.mark.parametrize("channels", [3, 2])
+def test_exp05_ally_observation_forms_agree(channels):
+    """te_observe_ally's two schedules on the same state: 4 096 envs take ally_view_kernel + ally_patch_kernel, their first 4 000
+    envs copied into a 4 000-env te_env take observe_ally_kernel (62 full chunks and one of 32 lanes).  Compared after 60 steps and
+    again after 180: a random-action rollout needs more than 60 steps before an invader reaches anybody (the oracle's census of this
+    rollout: 0 dead allies and one armed invader per env at steps 30, 60 and 90; 22 dead allies at step 150; 101 dead allies and 3 245
+    envs with two or more armed invaders at step 180), so the dead allies and the several armed invaders are asserted at step 180.
+    active and last_action are copies of state words: equal exactly.  lidar and inertial: at the commit before the two forms shared
+    their functions this test found them equal bit for bit at both steps and both channel counts (no word differed), so equality is
+    what it asserts."""
+    torch = _gpu()
+    from dronechase_amd import config as K
+    from dronechase_amd import default_config
+    from dronechase_amd.batched_env import BatchedEnv
+
+    NA, NB = 4096, 4000
+    A = BatchedEnv(default_config("exp05", n_envs=NA, motor_noise=1, seed=47, lidar_channels=channels), "cuda:0")
+    B = BatchedEnv(default_config("exp05", n_envs=NB, motor_noise=1, seed=47, lidar_channels=channels), "cuda:0")
+    D = A.D
+    A.reset()
+    for t in range(180):
+        A.set_ally_actions(A.random_actions(41, t))
+        A.step(A.random_actions(23, t))
+        if t + 1 not in (60, 180):
+            continue
+        state = A.get_state()
+        armed = state[: NA * D * K.DRONE_WORDS].view(NA, D, K.DRONE_WORDS)[:NB, :, K.D["ARMED"]] != 0
+        dead_allies, crowded = int((~armed[:, 1]).sum()), int((armed[:, 2:].sum(1) >= 2).sum())
+        B.set_state(torch.cat([state[: NB * D * K.DRONE_WORDS], state[NA * D * K.DRONE_WORDS:][: NB * K.ENV_WORDS]]))   # exp05 has no ring
+        (al, ai, aa, aact), (bl, bi, ba, bact) = A.observe_ally(), B.observe_ally()
+        al, ai, aa, aact = al[:NB], ai[:NB], aa[:NB], aact[:NB]
+        if t + 1 == 180:
+            assert dead_allies > 0 and crowded > 0    # neither only living allies nor a lone invader
+        assert bool((bl < 1).any()) and int(bact.sum()) == NB - dead_allies   # not an empty sphere
+        assert torch.equal(aact, bact) and torch.equal(aa, ba)
+        assert torch.equal(al, bl) and torch.equal(ai, bi)
+    A.close(); B.close()

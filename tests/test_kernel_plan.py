@@ -10,12 +10,14 @@ def sub(fam, fill, noise=T, ces=T, help=F):
     return f"substeps_kernel<{fam}, {noise}, {fill}, {ces}, {help}>"
 
 
-def plan(fam, engage, noise=T, ces=T, help=F, push=None, view=None):
+def plan(fam, engage, noise=T, ces=T, help=F, push=None, view=None, wingman=None):
     out = {"substeps": sub(fam, T, noise, ces, help), "substeps_nofill": sub(fam, F, noise, ces, help), "engage": engage}
     if push:
         out["ring_push"] = push
     if view:
         out["stack_view"] = view
+    if wingman:
+        out["wingman_view"] = wingman
     return out
 
 
@@ -24,6 +26,7 @@ S02_SLOTS = "engage_slots_stage02_kernel<16>"
 MULTI = "engage_slots_multi_kernel<{}, {}, {}>"
 V18, V37 = "stack_view_kernel<18>", "stack_view_kernel<37>"
 P18_4, P18_1, P37_1 = "ring_push_kernel<18, 4>", "ring_push_kernel<18, 1>", "ring_push_kernel<37, 1>"
+W1, W2 = "observe_ally_kernel", "ally_view_kernel+ally_patch_kernel"   # te_observe_wingman in one launch / in two
 
 # (task, n_envs, config overrides, environment knobs) -> kernels
 ROWS = [
@@ -40,8 +43,8 @@ ROWS = [
     ("stage03", 65536, {}, {}, plan(0, SLOTS)),
     ("exp04", 1024, {}, {}, plan(0, SLOTS, help=T)),
     ("exp04", 65536, {}, {}, plan(0, SLOTS)),
-    ("exp05", 1024, {}, {}, plan(0, SLOTS, help=T)),
-    ("exp05", 65536, {}, {}, plan(0, SLOTS)),
+    ("exp05", 1024, {}, {}, plan(0, SLOTS, help=T, wingman=W1)),
+    ("exp05", 65536, {}, {}, plan(0, SLOTS, wingman=W2)),
     ("evaluation", 1024, {}, {}, plan(0, SLOTS, help=T)),
     ("evaluation", 65536, {}, {}, plan(0, SLOTS)),
     ("level5", 1024, {}, {}, plan(0, MULTI.format(2, F, F), push=P18_4, view=V18)),
@@ -100,6 +103,14 @@ ROWS = [
     ("level5_fusion", 1024, {}, {"TE_STACKED": "lds"}, plan(0, MULTI.format(3, F, T), view="stacked_kernel")),
     ("stage03", 1024, {}, {"TE_DENSE_MIN": "1"}, plan(0, SLOTS, help=T)),
     ("stage03", 1024, {}, {"TE_FILL_WAVES": "512"}, plan(0, SLOTS, help=T)),
+    # a caller-driven pursuer's observation: two launches from 4 096 envs, when n_envs x lidar words is whole 16-byte quads
+    # (3 channels: 1 014 words, so an odd n_envs is not; 2 channels: 676 words, always) fewer than 2^32
+    ("exp05", 4095, {}, {}, plan(0, SLOTS, help=T, wingman=W1)),
+    ("exp05", 4096, {}, {}, plan(0, SLOTS, help=T, wingman=W2)),
+    ("exp05", 4097, {}, {}, plan(0, SLOTS, help=T, wingman=W1)),
+    ("exp05", 4097, {"lidar_channels": 2}, {}, plan(0, SLOTS, help=T, wingman=W2)),
+    # Evaluation_Task with both pursuers driven by the caller (9 rounds = te_calculate_rounds(2, 20)); the preset's own mask is 0: no line
+    ("evaluation", 65536, {"evaluation": 1 | (0b11 << 8), "n_pursuers": 2, "n_rounds": 9, "n_invaders": 9}, {}, plan(0, SLOTS, wingman=W2)),
 ]
 KNOBS = ("TE_ENGAGE", "TE_SLOT_SPW", "TE_K1_HELP", "TE_PUSH_SPLIT", "TE_STACKED", "TE_DENSE_MIN", "TE_FILL_WAVES")
 
