@@ -19,7 +19,7 @@
 // pursuer are te_wingman.hpp's.)
 // No MFMA: this is element-wise physics and byte streaming.  The MFMA kernels of the library are the policy's
 // inference, te_policy_act (te_policy.hpp) and te_drive_wingman's policy_drive_kernel (te_wingman.hpp), and its PPO gradient,
-// te_policy_ppo_grad (te_policy_grad.hpp); none is part of te_step.
+// te_policy_ppo_grad (te_policy_grad.hpp), and the optimiser step, te_policy_adam_step (te_policy_opt.hpp); none is part of te_step.
 //
 // Reference citations are file:line under the reference's src/ tree.
 #include <hip/hip_runtime.h>
@@ -44,6 +44,7 @@
 #include "te_policy.hpp"
 #include "te_wingman.hpp"
 #include "te_policy_grad.hpp"
+#include "te_policy_opt.hpp"
 #include "te_monitor.hpp"
 
 namespace te {
@@ -1755,6 +1756,50 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* param
   hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- optimiser step (te_policy_opt.hpp): every check is on the host, before any launch
+// words up to 2^40: the partials' count stays within int and the grid within its limit
+static int policy_opt_words_check(const char* fn, size_t words) {
+  if (words == 0) return fail(std::string(fn) + ": words must be positive");
+  if (words > ((size_t)1 << 40)) return fail(std::string(fn) + ": words must be at most 2^40");
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_opt_state_bytes(size_t words, size_t* out_bytes) {
+  if (!out_bytes) return fail("te_policy_opt_state_bytes: null argument");
+  if (policy_opt_words_check("te_policy_opt_state_bytes", words)) return 1;
+  *out_bytes = opt_layout(words).bytes;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_adam_step(float* params, const float* grad, void* state, size_t state_bytes, size_t words,
+                                                               double lr, double beta1, double beta2, double eps, float max_grad_norm,
+                                                               float grad_scale, void* stream) {
+  if (!params || !grad || !state) return fail("te_policy_adam_step: null argument");
+  if ((uintptr_t)params & 15) return fail("te_policy_adam_step: params must be 16-byte aligned");
+  if ((uintptr_t)grad & 15) return fail("te_policy_adam_step: grad must be 16-byte aligned");
+  if ((uintptr_t)state & 15) return fail("te_policy_adam_step: state must be 16-byte aligned");
+  if (policy_opt_words_check("te_policy_adam_step", words)) return 1;
+  const OptLayout o = opt_layout(words);
+  if (state_bytes < o.bytes)
+    return fail("te_policy_adam_step: state too small (" + std::to_string(state_bytes) + " bytes, te_policy_opt_state_bytes says " +
+                std::to_string(o.bytes) + ")");
+  if (!(lr >= 0.0) || !std::isfinite(lr)) return fail("te_policy_adam_step: lr must be finite and >= 0");
+  if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail("te_policy_adam_step: beta1 must be in [0, 1)");
+  if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail("te_policy_adam_step: beta2 must be in [0, 1)");
+  if (!(eps > 0.0) || !std::isfinite(eps)) return fail("te_policy_adam_step: eps must be finite and > 0");
+  if (!(max_grad_norm > 0.f)) return fail("te_policy_adam_step: max_grad_norm must be > 0 (INFINITY: no clipping)");
+  if (!std::isfinite(grad_scale)) return fail("te_policy_adam_step: grad_scale must be finite");
+  const AdamArgs a{lr, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, max_grad_norm, grad_scale};
+  const OptView view = opt_view(state, words);
+  const dim3 grid((unsigned)o.n_partials);
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(policy_gradnorm_kernel, grid, dim3(kOptThreads), 0, s, view, grad, grad_scale);
+  TE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(policy_adam_kernel, grid, dim3(kOptThreads), 0, s, view, params, grad, a);
   TE_HIP(hipGetLastError());
   return 0;
 }

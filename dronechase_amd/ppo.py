@@ -17,6 +17,8 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
     instead of ~40 PyTorch launches per step;
   * PPOConfig.fused_update: the minibatch's loss gradient in one ABI call (te_policy_ppo_grad, FusedPolicy.ppo_grad) instead of
     the PyTorch forward + autograd, reading the rollout rows through the minibatch index (no gather of the observations);
+  * PPOConfig.fused_optimizer: gradient clipping and Adam in one ABI call (te_policy_adam_step, PackedAdam) on the packed buffer the
+    kernels read, which the module's parameters are then views of (FusedPolicy.bind_parameters): no repack between minibatches;
   * PPOConfig.wingman_driver / PPO(wingman_policy=...): exp05's ally (and the evaluation task's "nn" drivers) flown by a frozen
     policy inside the rollout, one te_drive_wingman call per caller-driven pursuer before every te_step;
   * PPOConfig.episode_stats / PPO.evaluate: episode returns, lengths and final info rows accumulated on the device (monitor.py,
@@ -108,7 +110,8 @@ class FusedPolicy:
     """Inference of a LidarInertialActionPolicy by te_policy_act: the forward pass, the Gaussian sample, its log-prob and the
     clamp of the action in one HIP launch.  The weights are packed into ONE device buffer that keeps its address for the life of
     this object; refresh() repacks the module's current weights into it in place, so a HIP graph that captured a call sees them.
-    Call refresh() after every change of the module's weights (PPO does, at the start of every collect())."""
+    Call refresh() after every change of the module's weights (PPO does, at the start of every collect()).
+    After bind_parameters() the module's parameters are views of the packed buffer and there is nothing left to repack."""
 
     def __init__(self, policy: nn.Module):
         self.policy = policy
@@ -121,14 +124,33 @@ class FusedPolicy:
         if sum(p.numel() for p in params) != words:
             raise ValueError(f"policy has {sum(p.numel() for p in params)} parameters, te_policy_act's layout {words}: not a LidarInertialActionPolicy")
         self.params = torch.empty(words, dtype=torch.float32, device=self.device)
+        self.bound = False
         self.refresh()
 
     def refresh(self) -> None:
-        pack_policy(self.policy, out=self.params)
+        if not self.bound:      # bound: the parameters ARE the buffer (and torch.cat(out=) onto its own inputs raises)
+            pack_policy(self.policy, out=self.params)
+
+    @torch.no_grad()
+    def bind_parameters(self) -> None:
+        """Make every parameter of the module a view into the packed buffer, in _packed_order: from here on the buffer is the single
+        copy of the weights.  What te_policy_adam_step (PackedAdam) writes into it is what the PyTorch module, state_dict(),
+        te_policy_act and te_policy_ppo_grad read, and refresh() has nothing to do.  The offsets are multiples of 4 words except
+        log_std's, one word off (PyTorch does not mind).  copy.deepcopy of a bound module gets storage of its own; a .to() or .float()
+        that reallocates the parameters would detach them from the buffer: bind last."""
+        if self.bound:
+            return
+        self.refresh()
+        off = 0
+        for p in _packed_order(self.policy):
+            p.data = self.params[off:off + p.numel()].view_as(p)
+            off += p.numel()
+        self.bound = True
 
     @torch.no_grad()
     def load_from(self, module: nn.Module) -> None:
-        """Copy `module`'s weights into this object's policy and repack them in place: the packed buffer keeps its address, so a
+        """Copy `module`'s weights into this object's policy and repack them in place (bound: the copy lands in the packed buffer
+        through the views): the buffer keeps its address, so a
         HIP graph that captured a call flies the new weights.  A frozen snapshot of a learner is FusedPolicy(copy.deepcopy(learner))
         re-synced with load_from(learner)."""
         src, dst = _packed_order(module), _packed_order(self.policy)
@@ -213,6 +235,46 @@ class FusedPolicy:
         return a, logp, value, a_env
 
 
+class PackedAdam:
+    """clip_grad_norm_ + torch.optim.Adam (non-fused form, no weight decay, no amsgrad: SB3's optimiser) on a FusedPolicy's packed
+    buffer by te_policy_adam_step: two launches per step() on PyTorch's current stream, no host synchronisation, graph-capturable.
+    The state (step, the last call's norm and clip coefficient, exp_avg, exp_avg_sq) is ONE device buffer in the layout of
+    include/threatengage.h; zeros are a fresh optimiser.  Bind the policy's parameters (FusedPolicy.bind_parameters) for the module
+    to see the steps: this object writes fused_policy.params only."""
+
+    def __init__(self, fused_policy: FusedPolicy, lr: float, betas=(0.9, 0.999), eps: float = 1e-5):
+        self.fused_policy, self.lr, self.betas, self.eps = fused_policy, float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.words = fused_policy.params.numel()
+        need = C.c_size_t()
+        _lib.check(_lib.load().te_policy_opt_state_bytes(self.words, C.byref(need)), "te_policy_opt_state_bytes")
+        self.state = torch.zeros(int(need.value) // 4, dtype=torch.float32, device=fused_policy.device)
+        a = (self.words + 3) // 4 * 4            # m and v start on 16-byte boundaries behind the 64-byte header
+        self.step_count = self.state[0:1].view(torch.int32)    # views of the state: reading them costs no host synchronisation
+        self.grad_norm, self.clip_coef = self.state[1:2], self.state[2:3]
+        self.exp_avg, self.exp_avg_sq = self.state[16:16 + self.words], self.state[16 + a:16 + a + self.words]
+
+    def step(self, grad: torch.Tensor, max_grad_norm: float, grad_scale: float = 1.0) -> None:
+        """One clipped Adam step on `grad` [words] (the packed order, 16-byte aligned); max_grad_norm = inf does not clip;
+        grad_scale multiplies the gradient before the norm and the update (1 / world_size after an all-reduce)."""
+        f = self.fused_policy
+        require_f32("PackedAdam.step", "grad", grad, (self.words,), f.device)
+        with torch.cuda.device(f.device):
+            stream = torch.cuda.current_stream(f.device).cuda_stream
+            _lib.check(_lib.load().te_policy_adam_step(f.params.data_ptr(), grad.data_ptr(), self.state.data_ptr(), self.state.numel() * 4,
+                                                       self.words, self.lr, self.betas[0], self.betas[1], self.eps, float(max_grad_norm),
+                                                       float(grad_scale), stream), "te_policy_adam_step")
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        return {"state": self.state.clone()}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: Dict[str, torch.Tensor]) -> None:
+        src = sd["state"]
+        if tuple(src.shape) != tuple(self.state.shape) or src.dtype != self.state.dtype:
+            raise ValueError(f"PackedAdam.load_state_dict: the state must be {self.state.numel()} float32 words (te_policy_opt_state_bytes)")
+        self.state.copy_(src)
+
+
 class PolicyDriver:
     """SB3-style `predict` over a LidarInertialActionPolicy, on the device: what ThreatEngageVecEnv.update_model (exp05:
     the ally flown by a copy of the learning policy, apps/threatengage_runner/stage03/experiments/05/
@@ -269,6 +331,12 @@ class PPOConfig:
     # autograd; gradient clipping, the all-reduce and Adam stay as they are (with fast_learner: fused Adam, no autocast).
     # Off by default: the gradient agrees with autograd's to a tolerance (another summation order), not bit for bit
     fused_update: bool = False
+    # update(): gradient clipping and Adam in ONE ABI call (te_policy_adam_step, PackedAdam: two launches) instead of clip_grad_norm_ +
+    # torch.optim.Adam over 31 tensors.  Needs fused_update (the gradient already lies in the packed order) and a GPU.  The learner's
+    # parameters become views of the FusedPolicy's packed buffer (bind_parameters), so no repack follows a step, and update()'s dict
+    # gains "grad_norm" (the mean norm before clipping).  PPO.opt is then a PackedAdam (fast_learner's fused torch Adam is not used).
+    # Off by default: the step agrees with torch's to rounding (the norm is summed in another order), not bit for bit
+    fused_optimizer: bool = False
     reward_scale: float = 1e-3   # rewards reach +-1000 (exp03_vFinal_task.py:423-515); SB3 users wrap VecNormalize
     # who flies the caller-driven pursuers of the env (exp05's ally, the pursuers of cfg.evaluation's driver mask) during collect():
     # "none" = nobody, and PPO refuses such an env unless PPO(..., wingman_policy=module) gives a frozen policy to fly them;
@@ -283,6 +351,10 @@ class PPOConfig:
     # collect() carries over to the next.  Keys other than "ep_count" are absent when no episode finished.  With several GPUs the
     # statistics are rank-local (each rank's own env shard; no collective).  Off by default: collect()'s dict is unchanged
     episode_stats: bool = False
+
+    def __post_init__(self):
+        if self.fused_optimizer and not self.fused_update:
+            raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
 
 
 class RolloutBuffer:
@@ -396,10 +468,17 @@ class PPO:
         env.reset()
         if self.cfg.fused_forward and self.device.type != "cuda":
             raise ValueError("PPOConfig.fused_forward runs the HIP kernel te_policy_act: it needs a GPU device")
+        if self.cfg.fused_optimizer and self.device.type != "cuda":
+            raise ValueError("PPOConfig.fused_optimizer runs the HIP kernels of te_policy_adam_step: it needs a GPU device")
         if self.cfg.fused_update and self.device.type != "cuda":
             raise ValueError("PPOConfig.fused_update runs the HIP kernels of te_policy_ppo_grad: it needs a GPU device")
+        if self.cfg.fused_optimizer and not self.cfg.fused_update:      # set after PPOConfig's own check
+            raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
         self.fused = FusedPolicy(self.policy) if self.cfg.fused_forward else None
         self.fused_grad = (self.fused or FusedPolicy(self.policy)) if self.cfg.fused_update else None
+        if self.cfg.fused_optimizer:    # the packed buffer becomes the single copy of the weights; the torch optimiser is dropped
+            self.fused_grad.bind_parameters()
+            self.opt = PackedAdam(self.fused_grad, lr=self.cfg.learning_rate, eps=1e-5)
         self._grad_stats = torch.zeros(4, device=self.device)
         self.direct = env.N % 2 == 0   # slot t of the LIDAR buffer starts on a 16-byte boundary (4 056 bytes per env)
         self._obs = None               # set by the first collect(): te_observe of the reset state
@@ -567,7 +646,7 @@ class PPO:
         obs = {k: flat(v) for k, v in b.obs.items()}
         actions, old_logp, adv, ret = flat(b.actions), flat(b.logp), flat(b.adv), flat(b.ret)
         # running sums stay on the device: one host read per update(), not four per minibatch (each float() drains the stream)
-        acc = torch.zeros(4, device=self.device)
+        acc = torch.zeros(5 if c.fused_optimizer else 4, device=self.device)   # fused_optimizer: + the gradient's norm before clipping
         n_batches = 0
         amp = bool(c.fast_learner) and self.device.type == "cuda" and not c.fused_update
         for _ in range(c.n_epochs):
@@ -576,7 +655,9 @@ class PPO:
                 idx = perm[s:s + c.batch_size]
                 if self.fused_grad is not None:
                     self._fused_minibatch(obs, idx, actions, old_logp, adv, ret)
-                    acc += self._grad_stats
+                    acc[:4] += self._grad_stats
+                    if c.fused_optimizer:
+                        acc[4:] += self.opt.grad_norm
                     n_batches += 1
                     continue
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
@@ -601,19 +682,27 @@ class PPO:
                 with torch.no_grad():
                     acc += torch.stack((pg.detach(), vl.detach(), ent.detach(), ((ratio - 1).abs() > c.clip_range).float().mean()))
                 n_batches += 1
-        pg_s, vl_s, ent_s, clip_s = (acc / max(n_batches, 1)).tolist()
+        pg_s, vl_s, ent_s, clip_s, *norm_s = (acc / max(n_batches, 1)).tolist()
         self._updates_since_sync += 1
-        return {"pg_loss": pg_s, "v_loss": vl_s, "entropy": ent_s, "clip_frac": clip_s}
+        return {"pg_loss": pg_s, "v_loss": vl_s, "entropy": ent_s, "clip_frac": clip_s, **({"grad_norm": norm_s[0]} if norm_s else {})}
 
     def _fused_minibatch(self, obs, idx, actions, old_logp, adv, ret) -> None:
         """One minibatch of update() with fused_update: the gradient of the loss straight into the flat gradient bucket by
-        te_policy_ppo_grad, then the same all-reduce, clipping and Adam step as the autograd path."""
+        te_policy_ppo_grad, then the same all-reduce, clipping and Adam step as the autograd path; with fused_optimizer the all-reduce
+        and one te_policy_adam_step call on the buffer the next gradient reads (no repack, no division: grad_scale)."""
         c = self.cfg
-        self.fused_grad.refresh()            # Adam moved the weights: repack them (one 0.94 MB device copy)
+        self.fused_grad.refresh()            # Adam moved the weights: repack them (one 0.94 MB device copy; nothing when bound)
         a = adv[idx]
         ms = torch.stack((a.mean(), a.std()))
         self.fused_grad.ppo_grad(obs, idx, actions, old_logp, adv, ret, ms, c.clip_range, c.vf_coef, c.ent_coef,
                                  self._flat_grad, self._grad_stats)
+        if c.fused_optimizer:
+            world = 1
+            if self.distributed:
+                torch.distributed.all_reduce(self._flat_grad)
+                world = torch.distributed.get_world_size()
+            self.opt.step(self._flat_grad, c.max_grad_norm, grad_scale=1.0 / world)
+            return
         if self.distributed:
             torch.distributed.all_reduce(self._flat_grad)
             self._flat_grad.div_(torch.distributed.get_world_size())

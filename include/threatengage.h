@@ -485,6 +485,30 @@ int te_policy_ppo_grad(const float* params, int32_t lidar_channels, int32_t n, c
                        const float* ret, const float* adv_mean_std, float clip_range, float vf_coef, float ent_coef, float* grad,
                        float* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The optimiser step of the PPO learner: clip_grad_norm_ followed by torch.optim.Adam (the non-fused form; no weight decay, no
+ * amsgrad: SB3's optimiser) over ONE flat buffer of `words` fp32 parameters, e.g. the packed buffer of te_policy_act with the
+ * gradient of te_policy_ppo_grad.  The call knows nothing of the policy's layers: any words in [1, 2^40] is served.
+ *   s      = grad_scale * grad                      (a data-parallel caller passes 1 / world_size after its all-reduce)
+ *   norm   = ||s||_2;  coef = min(1, max_grad_norm / (norm + 1e-6));  g = coef * s
+ *   t      = step + 1;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2
+ *   params -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)      (fp32; the two bias corrections in fp64)
+ * max_grad_norm must be > 0; INFINITY means no clipping.  Non-finite gradients propagate as they do in torch.
+ *
+ * `state` is ONE caller-owned device buffer of te_policy_opt_state_bytes(words) bytes, 16-byte aligned; a zero-filled state is a
+ * fresh optimiser, and the buffer is saved and restored with a plain device copy.  Layout, with A = 4 * words rounded up to 16:
+ *   byte 0: step (i32, the number of calls so far);  byte 4: norm of the last call (f32, before clipping);  byte 8: coef of the last
+ *   call (f32);  bytes 12..63 reserved, zero;  byte 64: m [words] f32;  byte 64 + A: v [words] f32;  byte 64 + 2 A: the gradient
+ *   norm's partial sums, one f32 per 4 096 words, rounded up to 16 bytes (scratch: overwritten by every call).
+ * params and grad are 16-byte aligned.  Every sum has a fixed order and there are no atomics: a step depends on its inputs only, and
+ * repeated runs are bitwise equal.
+ * Two launches on `stream` (no allocation, no host synchronisation: a HIP graph can capture the call); runs on the current device.
+ * The step counter lives in the state, so every replay of a captured call advances it; lr and the other scalars are captured by
+ * value.  Every argument error (null pointer, misalignment, words == 0, state_bytes too small, lr < 0, a beta outside [0, 1),
+ * eps <= 0, max_grad_norm <= 0 or NaN, a non-finite grad_scale) returns before anything is launched. */
+int te_policy_opt_state_bytes(size_t words, size_t* out_bytes);
+int te_policy_adam_step(float* params, const float* grad, void* state, size_t state_bytes, size_t words, double lr, double beta1,
+                        double beta2, double eps, float max_grad_norm, float grad_scale, void* stream);
+
 /* Episode monitor: the bookkeeping of SB3's VecMonitor.step_wait (episode return and length per env, `infos[i]["episode"]`), of
  * its logger's ep_rew_mean / ep_len_mean window, and of evaluate_policy's per-env episode quotas (what the reference's
  * ReinforcementLearningPipeline.evaluate rests on, src/core/rl_framework/utils/pipeline.py:374-414), next to the step on the

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""The PPO learner's minibatch: autograd fp32 (plain Adam), PPOConfig.fast_learner (bf16 autocast + fused Adam) and
-PPOConfig.fused_update (te_policy_ppo_grad, te_policy_grad.hpp) at 8 192, 16 384 and 65 536 rows, each one update() of one
+"""The PPO learner's minibatch: autograd fp32 (plain Adam), PPOConfig.fast_learner (bf16 autocast + fused Adam),
+PPOConfig.fused_update (te_policy_ppo_grad, te_policy_grad.hpp) and fused_update + PPOConfig.fused_optimizer (te_policy_adam_step,
+te_policy_opt.hpp) at 2 048 (PPOConfig.batch_size's default), 8 192, 16 384 and 65 536 rows, each one update() of one
 minibatch (gradient + clip + Adam) on a collected stage03 rollout; the te_policy_ppo_grad call alone against its fp32 MFMA bound;
 then tools/ppo_split.py's 65 536-env collect + update with fused_forward=True, fused_update=True.  One JSON document on stdout.
     python tools/policy_update_bench.py [n_envs_for_split] [n_steps] [epochs]
@@ -34,16 +35,17 @@ def timed(fn, reps):
 
 
 out = {"macs_per_row": MACS_PER_ROW, "minibatch": []}
-for rows in (8192, 16384, 65536):
+for rows in (2048, 8192, 16384, 65536):
     rec = {"rows": rows, "bound_ms": 2.0 * MACS_PER_ROW * rows / (PEAK_TFLOPS * 1e12) * 1e3}
-    for key, kw in (("autograd_fp32_ms", {}), ("fast_learner_ms", {"fast_learner": True}), ("fused_update_ms", {"fused_update": True})):
+    for key, kw in (("autograd_fp32_ms", {}), ("fast_learner_ms", {"fast_learner": True}), ("fused_update_ms", {"fused_update": True}),
+                    ("fused_optimizer_ms", {"fused_update": True, "fused_optimizer": True})):
         env = BatchedEnv(default_config("stage03", n_envs=rows), "cuda:0")
         ppo = PPO(env, PPOConfig(n_steps=1, batch_size=rows, n_epochs=1, use_graph=False, **kw), seed=3)
         ppo.collect()
         for _ in range(3):
             ppo.update()                     # warm-up: MIOpen algorithm search, the fused path's workspace
         rec[key] = timed(ppo.update, 20) * 1e3
-        if "fused_update" in kw:            # the gradient call alone, on the same rows
+        if key == "fused_update_ms":        # the gradient call alone, on the same rows
             b = ppo.buf
             obs = {k: v.reshape(rows, *v.shape[2:]) for k, v in b.obs.items()}
             idx = torch.randperm(rows, device="cuda:0")
@@ -60,6 +62,7 @@ for rows in (8192, 16384, 65536):
         torch.cuda.empty_cache()
     rec["speedup_vs_autograd_fp32"] = rec["autograd_fp32_ms"] / rec["fused_update_ms"]
     rec["speedup_vs_fast_learner"] = rec["fast_learner_ms"] / rec["fused_update_ms"]
+    rec["fused_optimizer_speedup_vs_fused_update"] = rec["fused_update_ms"] / rec["fused_optimizer_ms"]
     out["minibatch"].append(rec)
 
 # tools/ppo_split.py's measurement with both fused paths on
