@@ -19,7 +19,8 @@
 // pursuer are te_wingman.hpp's.)
 // No MFMA: this is element-wise physics and byte streaming.  The MFMA kernels of the library are the policy's
 // inference, te_policy_act (te_policy.hpp) and te_drive_wingman's policy_drive_kernel (te_wingman.hpp), and its PPO gradient,
-// te_policy_ppo_grad (te_policy_grad.hpp), and the optimiser step, te_policy_adam_step (te_policy_opt.hpp); none is part of te_step.
+// te_policy_ppo_grad (te_policy_grad.hpp), the optimiser step, te_policy_adam_step (te_policy_opt.hpp), and the advantage arithmetic,
+// te_rollout_gae and te_adv_stats (te_rollout.hpp); none is part of te_step.
 //
 // Reference citations are file:line under the reference's src/ tree.
 #include <hip/hip_runtime.h>
@@ -45,6 +46,7 @@
 #include "te_wingman.hpp"
 #include "te_policy_grad.hpp"
 #include "te_policy_opt.hpp"
+#include "te_rollout.hpp"
 #include "te_monitor.hpp"
 
 namespace te {
@@ -1800,6 +1802,72 @@ __attribute__((visibility("default"))) int te_policy_adam_step(float* params, co
   hipLaunchKernelGGL(policy_gradnorm_kernel, grid, dim3(kOptThreads), 0, s, view, grad, grad_scale);
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(policy_adam_kernel, grid, dim3(kOptThreads), 0, s, view, params, grad, a);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- advantage estimation (te_rollout.hpp): every check is on the host, before any launch
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + b_bytes && y < x + a_bytes;
+}
+
+__attribute__((visibility("default"))) int te_rollout_gae(int32_t n_steps, int32_t n_envs, const float* rewards, const float* values,
+                                                          const float* dones, const float* last_value, double gamma, double gae_lambda,
+                                                          float* adv, float* ret, void* stream) {
+  if (!rewards || !values || !dones || !last_value || !adv || !ret) return fail("te_rollout_gae: null argument");
+  if (n_steps < 1) return fail("te_rollout_gae: n_steps must be positive");
+  if (n_envs < 1) return fail("te_rollout_gae: n_envs must be positive");
+  if ((int64_t)n_steps * n_envs > INT32_MAX) return fail("te_rollout_gae: n_steps * n_envs must be at most 2^31 - 1");
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return fail("te_rollout_gae: gamma must be in [0, 1]");
+  if (!(gae_lambda >= 0.0 && gae_lambda <= 1.0)) return fail("te_rollout_gae: gae_lambda must be in [0, 1]");
+  for (const void* q : {(const void*)rewards, (const void*)values, (const void*)dones, (const void*)last_value, (const void*)adv, (const void*)ret})
+    if ((uintptr_t)q & 3) return fail("te_rollout_gae: float arrays must be 4-byte aligned");
+  const size_t bytes = (size_t)n_steps * (size_t)n_envs * sizeof(float);
+  for (const void* q : {(const void*)rewards, (const void*)values, (const void*)dones, (const void*)last_value}) {
+    const size_t q_bytes = q == (const void*)last_value ? (size_t)n_envs * sizeof(float) : bytes;
+    if (ranges_overlap(adv, bytes, q, q_bytes) || ranges_overlap(ret, bytes, q, q_bytes))
+      return fail("te_rollout_gae: adv and ret must not alias the inputs");
+  }
+  if (ranges_overlap(adv, bytes, ret, bytes)) return fail("te_rollout_gae: adv and ret must not alias each other");
+  const GaeArgs a{rewards, values, dones, last_value, adv, ret, n_steps, n_envs, (float)gamma, (float)(gamma * gae_lambda)};
+  hipLaunchKernelGGL(rollout_gae_kernel, dim3((unsigned)((n_envs + kGaeThreads - 1) / kGaeThreads)), dim3(kGaeThreads), 0, (hipStream_t)stream, a);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+// n up to 2^40: the slice count stays within the grid's limit
+static int adv_stats_n_check(const char* fn, int64_t n) {
+  if (n < 1) return fail(std::string(fn) + ": n must be positive");
+  if (n > ((int64_t)1 << 40)) return fail(std::string(fn) + ": n must be at most 2^40");
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_adv_stats_workspace_bytes(int64_t n, size_t* out_bytes) {
+  if (!out_bytes) return fail("te_adv_stats_workspace_bytes: null argument");
+  if (adv_stats_n_check("te_adv_stats_workspace_bytes", n)) return 1;
+  *out_bytes = stat_workspace_bytes(n);
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_adv_stats(const float* x, const int64_t* index, int64_t n, float* out_mean_std, void* workspace,
+                                                        size_t workspace_bytes, void* stream) {
+  if (!x || !out_mean_std || !workspace) return fail("te_adv_stats: null argument");
+  if (adv_stats_n_check("te_adv_stats", n)) return 1;
+  if (((uintptr_t)x | (uintptr_t)out_mean_std) & 3) return fail("te_adv_stats: float arrays must be 4-byte aligned");
+  if ((uintptr_t)index & 7) return fail("te_adv_stats: index must be 8-byte aligned");
+  if ((uintptr_t)workspace & 7) return fail("te_adv_stats: workspace must be 8-byte aligned");
+  const size_t need = stat_workspace_bytes(n);
+  if (workspace_bytes < need)
+    return fail("te_adv_stats: workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_adv_stats_workspace_bytes says " +
+                std::to_string(need) + ")");
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t slices = stat_slices(n);
+  double* partials = static_cast<double*>(workspace);
+  if (index) hipLaunchKernelGGL(adv_stats_partial_kernel<true>, dim3((unsigned)slices), dim3(kStatThreads), 0, s, x, index, n, partials);
+  else hipLaunchKernelGGL(adv_stats_partial_kernel<false>, dim3((unsigned)slices), dim3(kStatThreads), 0, s, x, index, n, partials);
+  TE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(adv_stats_final_kernel, dim3(1), dim3(kStatThreads), 0, s, x, index, n, (const double*)partials, (int64_t)slices, out_mean_std);
   TE_HIP(hipGetLastError());
   return 0;
 }

@@ -19,6 +19,9 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
     the PyTorch forward + autograd, reading the rollout rows through the minibatch index (no gather of the observations);
   * PPOConfig.fused_optimizer: gradient clipping and Adam in one ABI call (te_policy_adam_step, PackedAdam) on the packed buffer the
     kernels read, which the module's parameters are then views of (FusedPolicy.bind_parameters): no repack between minibatches;
+  * PPOConfig.fused_advantages: GAE as one HIP launch over the whole rollout (te_rollout_gae, RolloutBuffer.finish(fused=True))
+    instead of ~9 PyTorch launches per step, the minibatch's advantage mean and std as one te_adv_stats call (adv_stats below)
+    into the two floats te_policy_ppo_grad reads, and "explained_variance" in update()'s log;
   * PPOConfig.wingman_driver / PPO(wingman_policy=...): exp05's ally (and the evaluation task's "nn" drivers) flown by a frozen
     policy inside the rollout, one te_drive_wingman call per caller-driven pursuer before every te_step;
   * PPOConfig.episode_stats / PPO.evaluate: episode returns, lengths and final info rows accumulated on the device (monitor.py,
@@ -275,6 +278,34 @@ class PackedAdam:
         self.state.copy_(src)
 
 
+def adv_stats_workspace(n: int, device) -> torch.Tensor:
+    """The workspace of adv_stats for up to n elements (te_adv_stats_workspace_bytes is monotone in n)."""
+    need = C.c_size_t()
+    _lib.check(_lib.load().te_adv_stats_workspace_bytes(int(n), C.byref(need)), "te_adv_stats_workspace_bytes")
+    return torch.empty(int(need.value), dtype=torch.uint8, device=device)
+
+
+def adv_stats(x: torch.Tensor, index: Optional[torch.Tensor], out: torch.Tensor, workspace: torch.Tensor) -> None:
+    """out[0], out[1] = the mean and the unbiased std (torch.std's default) of x[index] (int64 [B]; None: all of x), x a contiguous
+    float32 vector: one te_adv_stats call, two launches on PyTorch's current stream, fp64 sums in a fixed order (repeated calls are
+    bitwise equal), no host synchronisation, graph-capturable.  `workspace` comes from adv_stats_workspace(n) with n >= the count."""
+    dev = x.device
+    if dev.type != "cuda":
+        raise ValueError("adv_stats runs the HIP kernels of te_adv_stats: x must live on a GPU")
+    if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("adv_stats: x must be a contiguous 1-D float32 tensor")
+    require_f32("adv_stats", "out", out, (2,), dev)
+    if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != dev or not index.is_contiguous()):
+        raise ValueError(f"adv_stats: index must be a contiguous 1-D int64 tensor on {dev}")
+    if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"adv_stats: workspace must be a contiguous uint8 tensor on {dev} (adv_stats_workspace)")
+    n = x.numel() if index is None else index.numel()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.load().te_adv_stats(x.data_ptr(), _ptr(index), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(), stream),
+                   "te_adv_stats")
+
+
 class PolicyDriver:
     """SB3-style `predict` over a LidarInertialActionPolicy, on the device: what ThreatEngageVecEnv.update_model (exp05:
     the ally flown by a copy of the learning policy, apps/threatengage_runner/stage03/experiments/05/
@@ -351,6 +382,14 @@ class PPOConfig:
     # collect() carries over to the next.  Keys other than "ep_count" are absent when no episode finished.  With several GPUs the
     # statistics are rank-local (each rank's own env shard; no collective).  Off by default: collect()'s dict is unchanged
     episode_stats: bool = False
+    # the advantage arithmetic between the rollout and the gradient call in HIP (te_rollout.hpp).  collect(): GAE as ONE launch over the
+    # whole rollout (te_rollout_gae, one thread per env) instead of RolloutBuffer.finish's ~9 PyTorch launches per step; adv and ret are
+    # bitwise what finish() gives.  update() with fused_update: the minibatch's advantage mean and std by one te_adv_stats call (two
+    # launches, fp64 sums in a fixed order) into the two floats te_policy_ppo_grad reads, instead of gather + mean + std + stack; they
+    # agree with torch's to rounding, not bit for bit.  update()'s dict gains "explained_variance" = 1 - Var(ret - values) / Var(ret)
+    # over the rollout (SB3's logger key; NaN when Var(ret) is 0), from two more te_adv_stats calls; with several GPUs it is rank-local
+    # (each rank's own rollout; no collective).  Needs a GPU, not fused_update.  Off by default: every dict, tensor and launch is unchanged
+    fused_advantages: bool = False
 
     def __post_init__(self):
         if self.fused_optimizer and not self.fused_update:
@@ -376,9 +415,23 @@ class RolloutBuffer:
         return sum(t.numel() * t.element_size() for t in ts)
 
     @torch.no_grad()
-    def finish(self, last_value: torch.Tensor, gamma: float, lam: float) -> None:
+    def finish(self, last_value: torch.Tensor, gamma: float, lam: float, fused: bool = False) -> None:
         """GAE(lambda).  An env that auto-reset at step t starts a new episode at t+1: no bootstrap across it
-        (terminations only: the reference never truncates, exp03_vFinal_environment.py:166)."""
+        (terminations only: the reference never truncates, exp03_vFinal_environment.py:166).
+        fused=True: the same recurrence, operation for operation, as ONE te_rollout_gae launch on PyTorch's current stream
+        (bitwise the same adv and ret; GPU only)."""
+        if fused:
+            T, N = self.rewards.shape
+            dev = self.rewards.device
+            if dev.type != "cuda":
+                raise ValueError("RolloutBuffer.finish(fused=True) runs the HIP kernel te_rollout_gae: the buffer must live on a GPU")
+            require_f32("RolloutBuffer.finish", "last_value", last_value, (N,), dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.check(_lib.load().te_rollout_gae(T, N, self.rewards.data_ptr(), self.values.data_ptr(), self.dones.data_ptr(),
+                                                      last_value.data_ptr(), float(gamma), float(lam), self.adv.data_ptr(),
+                                                      self.ret.data_ptr(), stream), "te_rollout_gae")
+            return
         gae = torch.zeros_like(last_value)
         nxt = last_value
         for t in reversed(range(self.rewards.shape[0])):
@@ -472,6 +525,8 @@ class PPO:
             raise ValueError("PPOConfig.fused_optimizer runs the HIP kernels of te_policy_adam_step: it needs a GPU device")
         if self.cfg.fused_update and self.device.type != "cuda":
             raise ValueError("PPOConfig.fused_update runs the HIP kernels of te_policy_ppo_grad: it needs a GPU device")
+        if self.cfg.fused_advantages and self.device.type != "cuda":
+            raise ValueError("PPOConfig.fused_advantages runs the HIP kernels of te_rollout_gae and te_adv_stats: it needs a GPU device")
         if self.cfg.fused_optimizer and not self.cfg.fused_update:      # set after PPOConfig's own check
             raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
         self.fused = FusedPolicy(self.policy) if self.cfg.fused_forward else None
@@ -480,6 +535,10 @@ class PPO:
             self.fused_grad.bind_parameters()
             self.opt = PackedAdam(self.fused_grad, lr=self.cfg.learning_rate, eps=1e-5)
         self._grad_stats = torch.zeros(4, device=self.device)
+        if self.cfg.fused_advantages:   # allocated once, for the whole rollout: nothing grows under graph capture
+            self._adv_stats = torch.zeros(2, device=self.device)         # the minibatch's (mean, std): te_policy_ppo_grad's adv_mean_std
+            self._ev_stats = torch.zeros(4, device=self.device)          # (mean, std) of adv and of ret over the rollout
+            self._adv_ws = adv_stats_workspace(self.cfg.n_steps * env.N, self.device)
         self.direct = env.N % 2 == 0   # slot t of the LIDAR buffer starts on a 16-byte boundary (4 056 bytes per env)
         self._obs = None               # set by the first collect(): te_observe of the reset state
         self.monitor = None
@@ -570,7 +629,7 @@ class PPO:
                 self.monitor.step(self.env.reward, self.env.done, self.env.info)
         self._obs = self._g_obs
         _, last_v = (self.fused or self.policy)(self._obs)
-        b.finish(last_v, c.gamma, c.gae_lambda)
+        b.finish(last_v, c.gamma, c.gae_lambda, fused=c.fused_advantages)
         self.num_timesteps += c.n_steps * self.env.N
         return {"mean_step_reward": float(ep_rew) / c.n_steps, "episodes_finished": int(ep_n), **self._episode_stats()}
 
@@ -618,7 +677,7 @@ class PPO:
         self._obs = {"lidar": lidar, "inertial_data": inertial, "last_action": last_action}
         _, last_v = (self.fused or self.policy)(self._obs)
         ep_rew, ep_n = float(ep_rew), int(ep_n)
-        b.finish(last_v, c.gamma, c.gae_lambda)
+        b.finish(last_v, c.gamma, c.gae_lambda, fused=c.fused_advantages)
         self.num_timesteps += c.n_steps * self.env.N
         return {"mean_step_reward": ep_rew / c.n_steps, "episodes_finished": ep_n, **self._episode_stats()}
 
@@ -648,6 +707,9 @@ class PPO:
         # running sums stay on the device: one host read per update(), not four per minibatch (each float() drains the stream)
         acc = torch.zeros(5 if c.fused_optimizer else 4, device=self.device)   # fused_optimizer: + the gradient's norm before clipping
         n_batches = 0
+        if c.fused_advantages:          # explained_variance's two stds, on the device: read with the accumulators below
+            adv_stats(adv, None, self._ev_stats[0:2], self._adv_ws)
+            adv_stats(ret, None, self._ev_stats[2:4], self._adv_ws)
         amp = bool(c.fast_learner) and self.device.type == "cuda" and not c.fused_update
         for _ in range(c.n_epochs):
             perm = torch.randperm(T * N, device=self.device)
@@ -682,9 +744,18 @@ class PPO:
                 with torch.no_grad():
                     acc += torch.stack((pg.detach(), vl.detach(), ent.detach(), ((ratio - 1).abs() > c.clip_range).float().mean()))
                 n_batches += 1
-        pg_s, vl_s, ent_s, clip_s, *norm_s = (acc / max(n_batches, 1)).tolist()
+        means = acc / max(n_batches, 1)
+        if c.fused_advantages:
+            means = torch.cat((means, self._ev_stats))
+        pg_s, vl_s, ent_s, clip_s, *rest = means.tolist()
         self._updates_since_sync += 1
-        return {"pg_loss": pg_s, "v_loss": vl_s, "entropy": ent_s, "clip_frac": clip_s, **({"grad_norm": norm_s[0]} if norm_s else {})}
+        out = {"pg_loss": pg_s, "v_loss": vl_s, "entropy": ent_s, "clip_frac": clip_s}
+        if c.fused_optimizer:
+            out["grad_norm"] = rest[0]
+        if c.fused_advantages:          # ret - values is the advantage: 1 - Var(adv) / Var(ret), SB3's explained_variance
+            std_adv, std_ret = rest[-3], rest[-1]
+            out["explained_variance"] = float("nan") if std_ret == 0.0 else 1.0 - (std_adv * std_adv) / (std_ret * std_ret)
+        return out
 
     def _fused_minibatch(self, obs, idx, actions, old_logp, adv, ret) -> None:
         """One minibatch of update() with fused_update: the gradient of the loss straight into the flat gradient bucket by
@@ -692,8 +763,12 @@ class PPO:
         and one te_policy_adam_step call on the buffer the next gradient reads (no repack, no division: grad_scale)."""
         c = self.cfg
         self.fused_grad.refresh()            # Adam moved the weights: repack them (one 0.94 MB device copy; nothing when bound)
-        a = adv[idx]
-        ms = torch.stack((a.mean(), a.std()))
+        if c.fused_advantages:
+            adv_stats(adv, idx, self._adv_stats, self._adv_ws)
+            ms = self._adv_stats
+        else:
+            a = adv[idx]
+            ms = torch.stack((a.mean(), a.std()))
         self.fused_grad.ppo_grad(obs, idx, actions, old_logp, adv, ret, ms, c.clip_range, c.vf_coef, c.ent_coef,
                                  self._flat_grad, self._grad_stats)
         if c.fused_optimizer:

@@ -509,6 +509,37 @@ int te_policy_opt_state_bytes(size_t words, size_t* out_bytes);
 int te_policy_adam_step(float* params, const float* grad, void* state, size_t state_bytes, size_t words, double lr, double beta1,
                         double beta2, double eps, float max_grad_norm, float grad_scale, void* stream);
 
+/* The PPO learner's advantage arithmetic between the rollout and the gradient call (dronechase_amd/ppo.py RolloutBuffer.finish and
+ * the minibatch's advantage normalisation).  Neither call knows the policy or the environments.
+ *
+ * te_rollout_gae: GAE(lambda) over a rollout of n_steps x n_envs.  rewards, values, dones (1.0 where the env finished AFTER the step,
+ * else 0.0), adv and ret are contiguous [n_steps][n_envs] f32, last_value [n_envs] is the value of the state after the last step;
+ * 4-byte alignment is all that is asked (n_envs may be odd).  For every env, with nxt = last_value, gae = 0 and t = n_steps - 1 ... 0:
+ *   nt    = 1 - dones[t]
+ *   delta = (rewards[t] + (fl32(gamma) nxt) nt) - values[t]
+ *   gae   = delta + (fl32(gamma gae_lambda) nt) gae           (the product gamma gae_lambda is formed in double on the host)
+ *   adv[t] = gae;  ret[t] = gae + values[t];  nxt = values[t]
+ * Every operation is rounded to fp32 on its own (no fused multiply-add), in this order: the result is bitwise what the same
+ * recurrence gives as one PyTorch op per operation.  adv and ret must not overlap the inputs or each other (refused).
+ * n_steps, n_envs >= 1, n_steps n_envs <= 2^31 - 1, gamma and gae_lambda in [0, 1].  One launch on `stream`, one thread per env.
+ *
+ * te_adv_stats: out_mean_std[0] = the mean and out_mean_std[1] = the unbiased standard deviation (torch.std's default; NaN for
+ * n = 1) of the n elements x[index[i]] (index: int64, device, not range-checked; NULL reads x[i]): the adv_mean_std of
+ * te_policy_ppo_grad.  The sums are fp64, of x - x[index[0]] and its square, over fixed slices of 4 096 elements with a fixed tree
+ * inside a slice and the slices in index order: no atomics, repeated calls are bitwise equal, an indexed call equals the call on the
+ * gathered elements, and a constant input has a std of exactly 0.  workspace: device memory, 8-byte aligned, of at least
+ * te_adv_stats_workspace_bytes(n) bytes (16 per slice, a multiple of 16; overwritten by every call).  1 <= n <= 2^40.  Two launches
+ * on `stream`.
+ *
+ * Both calls allocate nothing and do not synchronise with the host (a HIP graph can capture them) and run on the current device.
+ * Every argument error (null pointer, misalignment, a size out of range, gamma or gae_lambda outside [0, 1] or not finite,
+ * overlapping outputs, a workspace too small) returns before anything is launched. */
+int te_rollout_gae(int32_t n_steps, int32_t n_envs, const float* rewards, const float* values, const float* dones,
+                   const float* last_value, double gamma, double gae_lambda, float* adv, float* ret, void* stream);
+int te_adv_stats_workspace_bytes(int64_t n, size_t* out_bytes);
+int te_adv_stats(const float* x, const int64_t* index, int64_t n, float* out_mean_std, void* workspace, size_t workspace_bytes,
+                 void* stream);
+
 /* Episode monitor: the bookkeeping of SB3's VecMonitor.step_wait (episode return and length per env, `infos[i]["episode"]`), of
  * its logger's ep_rew_mean / ep_len_mean window, and of evaluate_policy's per-env episode quotas (what the reference's
  * ReinforcementLearningPipeline.evaluate rests on, src/core/rl_framework/utils/pipeline.py:374-414), next to the step on the
