@@ -12,7 +12,10 @@ shift = 0 the mean's condition number is about sqrt(n) and the relative bound on
 every x - mean carries the fp32 rounding of a number near 100 (4e-6 absolute against a std of 1), so an fp32 std is good to about
 1e-6, not 2.4e-7.  Measured on the MI355X, as fractions of the (single) bounds: te_adv_stats at most 0.83 (mean) and 0.43 (std)
 over every size and set; torch fp32 at most 1.93 and 0.85 at shift = 1, but 36 (mean, shift 0, n = 65) and 7.8 (std, shift 100,
-n = 64), which is what the fp64 sums and the shifted set are there for.  The gaps of both are printed for every case (pytest -s)."""
+n = 64), which is what the fp64 sums and the shifted set are there for.  The gaps of both are printed for every case (pytest -s).
+Past 256 slices (LOOP_SIZES, test_stats_past_256_slices: the sizes at which the final kernel's threads take more than one partial
+each, as they do at the workload's 2 048 slices) the same bounds hold on a trend plus noise, torch's fp32 sums held to nothing:
+measured at most 0.86 (mean) and 0.40 (std)."""
 import ctypes as C
 import math
 import os
@@ -25,6 +28,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SLICE = 4096                     # kStatSlice: the elements one workgroup owns
 GAE_SHAPES = ((1, 1), (7, 5), (3, 64), (5, 65), (128, 257))
 STAT_SIZES = (1, 2, 63, 64, 65, SLICE - 1, SLICE, SLICE + 1, 2 * SLICE + 3, 300000)
+# adv_stats_final_kernel's 256 threads each take partials t, t + 256, ...: 256 slices is the last size with one trip, at 257 thread 0
+# alone takes a second partial (of a one-element slice), at 514 every thread takes two trips or three and the last slice is ragged
+LOOP_SIZES = (256 * SLICE, 256 * SLICE + 1, 513 * SLICE + 5)
 GAMMA, LAM = 0.99, 0.95
 SHIFTS = (0.0, 1.0, 100.0)
 TORCH_SHIFT = 1.0                # the set torch's fp32 reductions are held to twice the bounds on (module docstring)
@@ -53,8 +59,9 @@ def test_symbols_declared_and_exported(lib):
 
 
 def test_workspace_bytes(lib):
-    sizes = (1, 2, SLICE - 1, SLICE, SLICE + 1, 2 * SLICE + 3, 300000, 128 * 65536, 1 << 31, 1 << 40)
+    sizes = (1, 2, SLICE - 1, SLICE, SLICE + 1, 2 * SLICE + 3, 300000, *LOOP_SIZES, 128 * 65536, 1 << 31, 1 << 40)
     got = [_ws_bytes(lib, n) for n in sizes]
+    assert [_ws_bytes(lib, n) for n in LOOP_SIZES] == [16 * 256, 16 * 257, 16 * 514]
     assert all(a <= b for a, b in zip(got, got[1:])), got
     for n, b in zip(sizes, got):
         assert b % 16 == 0 and b == 16 * ((n + SLICE - 1) // SLICE), (n, b)      # the documented size: two fp64 partials per slice
@@ -254,6 +261,54 @@ def test_stats_against_fp64(n, shift):
               f" (of twice the bound: {tm / 2:.3f}, {ts / 2:.3f})")
         if shift == TORCH_SHIFT:
             assert tm <= 2.0 and ts <= 2.0, "the inputs are wrong: torch fp32 itself misses twice the bound"
+        assert gm <= 1.0 and gs <= 1.0, (name, mean, std, ref)
+
+
+_TREND_INPUTS = {}
+
+
+def _trend_inputs(torch, n):
+    """As _stat_inputs, for the sizes past 256 slices, with a trend under the noise: x[i] = i / n + 0.1 N(0, 1) and big[j] = j / m +
+    0.1 N(0, 1), m = 2 n + 5, in float32.  The slices of x then have different sums (a slice is worth about SLICE / n of the mean,
+    2e-3 and more, against a bound near 3e-8), so a partial that is dropped, doubled or taken from another slice shows; the rows
+    big[idx] lose the trend's order, not its spread.  Worked out in fp64 for these seeds: leaving any one slice out of the final sum,
+    the one-element slice of 257 included, moves the mean or the std by at least 8 bounds (plain: 29), the first 256 partials alone
+    at 514 slices by 1e6."""
+    if n not in _TREND_INPUTS:
+        rng = np.random.default_rng(9000 + n)
+        m = 2 * n + 5
+        x = (np.arange(n) / n + 0.1 * rng.standard_normal(n)).astype(np.float32)
+        big = (np.arange(m) / m + 0.1 * rng.standard_normal(m)).astype(np.float32)
+        idx = rng.integers(0, m, n)
+        idx[1] = idx[0]             # at least one repeat
+
+        def ref(a):
+            a = a.astype(np.float64)
+            return float(a.mean()), float(a.std(ddof=1)), float(np.abs(a).max())
+
+        dev = lambda a: torch.from_numpy(a).to("cuda:0")
+        _TREND_INPUTS[n] = (dev(x), dev(big), dev(idx.astype(np.int64)), ref(x), ref(big[idx]))
+    return _TREND_INPUTS[n]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", LOOP_SIZES)
+def test_stats_past_256_slices(n):
+    """The second-level sum beyond one trip per thread (LOOP_SIZES), against fp64 numpy on the same fp32 elements and the bounds of the
+    module docstring: the kernel sums in fp64 about a pivot and rounds once, so its error does not grow with n.  torch's fp32 sums do
+    grow with n and are held to nothing here."""
+    torch = _gpu()
+    assert (n + SLICE - 1) // SLICE in (256, 257, 514)
+    x, big, idx, ref_x, ref_idx = _trend_inputs(torch, n)
+    for name, src, index, ref in (("plain", x, None, ref_x), ("indexed", big, idx, ref_idx)):
+        out = _stats(torch, src, index)
+        mean, std = float(out[0]), float(out[1])
+        # the same call again, with a larger workspace: bitwise the same; an indexed call equals the call on the gathered rows
+        assert torch.equal(_bits(out), _bits(_stats(torch, src, index, n_ws=2 * n + 7)))
+        if index is not None:
+            assert torch.equal(_bits(out), _bits(_stats(torch, src[index].contiguous(), None)))
+        gm, gs = _gaps(mean, std, ref)
+        print(f"\nn={n} ({(n + SLICE - 1) // SLICE} slices) {name}: gap / bound: te_adv_stats mean {gm:.3f} std {gs:.3f}")
         assert gm <= 1.0 and gs <= 1.0, (name, mean, std, ref)
 
 
