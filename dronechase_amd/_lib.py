@@ -17,6 +17,7 @@ EXPORTS = (
     "te_config_default", "te_create", "te_destroy", "te_reset", "te_observe", "te_step", "te_random_actions",
     "te_state_words", "te_get_state", "te_set_state", "te_algorithmic_bytes_per_env_step", "te_profile_begin",
     "te_profile_end", "te_debug_stamps", "te_abi_version", "te_last_error", "te_step_stacked", "te_observe_stacked", "te_observe_ally", "te_set_ally_actions", "te_wingman_info", "te_calculate_rounds", "te_observe_wingman", "te_set_wingman_actions", "te_drive_wingman", "te_quad_preset", "te_step_students", "te_set_persistent_obs",
+    "te_policy_shape_check", "te_policy_param_words_shaped", "te_policy_act_shaped", "te_drive_wingman_shaped",
     "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad", "te_kernel_plan",
     "te_policy_opt_state_bytes", "te_policy_adam_step",
     "te_rollout_gae", "te_adv_stats_workspace_bytes", "te_adv_stats",
@@ -31,6 +32,11 @@ class TEError(RuntimeError):
 class MonitorOffsets(C.Structure):
     """te_monitor_offsets: byte offsets of the arrays inside an episode-monitor buffer (include/threatengage.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("bytes", "n_rows", "rows", "ret", "len", "episodes", "last_ret", "last_len", "rec_info", "rec_ret", "rec_len")]
+
+
+class PolicyShape(C.Structure):
+    """te_policy_shape: the policy's LIDAR channels, trunk width and head widths (include/threatengage.h)."""
+    _fields_ = [("lidar_channels", C.c_int32), ("features_dim", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 4)]
 
 
 def load() -> C.CDLL:
@@ -79,6 +85,11 @@ def load() -> C.CDLL:
     L.te_profile_end.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)]
     L.te_policy_param_words.argtypes = [i32, C.POINTER(C.c_size_t)]
     L.te_policy_act.argtypes = [vp, i32, i32] + [vp] * 9 + [vp]
+    shape = C.POINTER(PolicyShape)
+    L.te_policy_shape_check.argtypes = [shape]
+    L.te_policy_param_words_shaped.argtypes = [shape, C.POINTER(C.c_size_t)]
+    L.te_policy_act_shaped.argtypes = [vp, shape, i32] + [vp] * 9 + [vp]
+    L.te_drive_wingman_shaped.argtypes = [vp, i32, vp, shape] + [vp] * 4 + [vp]
     L.te_policy_grad_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
     f32 = C.c_float
     L.te_policy_ppo_grad.argtypes = [vp, i32, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]

@@ -189,8 +189,8 @@ class BatchedEnv:
             raise ValueError(f"drive_wingman: the policy lives on {fused_policy.device}, the env on {self.device}")
         if mu is not None:
             require_f32("drive_wingman", "mu", mu, (self.N, 4), self.device, shown=f"[{self.N}, 4]")
-        _lib.check(self.L.te_drive_wingman(self._h, int(wingman), self._p(fused_policy.params), int(fused_policy.lidar_channels), self._p(lidar),
-                                           self._p(inertial), self._p(last_action), self._p(mu), self._stream()), "te_drive_wingman")
+        _lib.check(self.L.te_drive_wingman_shaped(self._h, int(wingman), self._p(fused_policy.params), C.byref(fused_policy.shape), self._p(lidar),
+                                                  self._p(inertial), self._p(last_action), self._p(mu), self._stream()), "te_drive_wingman_shaped")
 
     def observe_ally(self):
         """exp05: the ally = pursuer 1 (Exp05_vFinal_Task.compute_lw_observation)."""

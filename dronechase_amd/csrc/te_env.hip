@@ -31,6 +31,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <new>
 #include <string>
 #include <tuple>
@@ -1048,26 +1050,76 @@ static hipError_t set_lds_limits(const KernelPlan& k) {   // dynamic LDS beyond 
   return hipSuccess;
 }
 
-// The launch of a policy kernel template's <2> or <3> instance (K2, K3: kernel(PolicyParams, args...)) on the tile grid of n rows.  kPolLdsBytes
-// is above the 64 KB a launch gets by default: opt in once per (device, instance, in `opted`); not a stream operation, so a capturing stream allows it.
-template <auto K2, auto K3, class... Args>
-static int policy_launch(int32_t lidar_channels, const float* params, int n, void* stream, const Args&... args) {
-  static uint64_t opted[2] = {0, 0};
-  uint64_t& bits = opted[lidar_channels - 2];
+// The launch of one instance of a policy kernel template (ks[shape id][C - 2]: kernel(PolicyParams, args...)) on the shape's tile grid of n
+// rows.  A shape's LDS is above the 64 KB a launch gets by default: opt in once per (device, instance, in `opted`); not a stream operation, so a
+// capturing stream allows it.
+template <class... Args>
+using PolKernel = void (*)(PolicyParams, Args...);
+template <class T>
+struct PolArg { using type = T; };   // the arguments convert to the kernel's formals; they do not deduce them
+
+template <int NS, class... Args>
+static int policy_launch(PolKernel<Args...> const (&ks)[NS][2], int shape_id, int32_t lidar_channels, const float* params, int n, void* stream,
+                         const typename PolArg<Args>::type&... args) {
+  static std::map<const void*, uint64_t> opted;
+  static std::mutex opted_lock;
+  const PolShape shape = pol_shape(shape_id, lidar_channels);
+  const PolLds lds = pol_lds_plan(shape);
+  const PolKernel<Args...> fn = ks[shape_id][lidar_channels - 2];
   int dev = 0;
   TE_HIP(hipGetDevice(&dev));
-  if (dev < 64 && !(bits >> dev & 1)) {
-    TE_HIP(hipFuncSetAttribute(lidar_channels == 3 ? reinterpret_cast<const void*>(K3) : reinterpret_cast<const void*>(K2),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes));
-    bits |= 1ull << dev;
+  {
+    std::lock_guard<std::mutex> hold(opted_lock);
+    uint64_t& bits = opted[reinterpret_cast<const void*>(fn)];
+    if (dev < 64 && !(bits >> dev & 1)) {
+      TE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds.words * 4));
+      bits |= 1ull << dev;
+    }
   }
-  PolicyParams P = policy_layout(lidar_channels);
+  PolicyParams P = policy_layout(shape);
   P.base = params;
-  const dim3 grid((unsigned)((n + kPolTileM - 1) / kPolTileM));
-  if (lidar_channels == 3) hipLaunchKernelGGL(K3, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, args...);
-  else hipLaunchKernelGGL(K2, grid, dim3(kPolThreads), kPolLdsBytes, (hipStream_t)stream, P, args...);
+  const dim3 grid((unsigned)((n + lds.M - 1) / lds.M));
+  hipLaunchKernelGGL(fn, grid, dim3(kPolThreads), (size_t)lds.words * 4, (hipStream_t)stream, P, args...);
   TE_HIP(hipGetLastError());
   return 0;
+}
+
+// every served instance of an inference kernel template K<C, shape id>
+#define TE_POL_INSTANCES(K) \
+  {{&K<2, POL_SHAPE_DEFAULT>, &K<3, POL_SHAPE_DEFAULT>}, {&K<2, POL_SHAPE_BO>, &K<3, POL_SHAPE_BO>}, {&K<2, POL_SHAPE_LEARN>, &K<3, POL_SHAPE_LEARN>}}
+static_assert(POL_SHAPE_COUNT == 3, "TE_POL_INSTANCES lists every shape");
+static const PolKernel<PolicyIO> kPolicyActKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_act_kernel);
+static const PolKernel<PolicyIn, Params, int, float*> kPolicyDriveKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_drive_kernel);
+static const PolKernel<PolicyIn, GradTileArgs> kPolicyGradKernels[1][2] = {{&policy_grad_tile_kernel<2>, &policy_grad_tile_kernel<3>}};
+
+static std::string shape_text(const PolShape& s) {
+  std::string t = "features_dim " + std::to_string(s.F) + ", hidden";
+  for (int i = 0; i < s.n_hidden; ++i) t += (i ? ", " : " ") + std::to_string(s.h[i]);
+  return t;
+}
+
+// The id of a served shape, or -1 with the message in g_err.  Host only: no device call.
+static int policy_shape_id(const te_policy_shape* s, const char* fn) {
+  const std::string who = std::string(fn) + ": ";
+  if (!s) return fail(who + "null shape"), -1;
+  std::string served = "; the served shapes, for lidar_channels 2 and 3:";
+  for (int id = 0; id < POL_SHAPE_COUNT; ++id) served += (id ? " | " : " ") + shape_text(pol_shape(id, 3));
+  if (s->lidar_channels != 2 && s->lidar_channels != 3)
+    return fail(who + "lidar_channels must be 2 or 3, not " + std::to_string(s->lidar_channels) + served), -1;
+  if (s->n_hidden < 1 || s->n_hidden > 3) return fail(who + "n_hidden must be 1, 2 or 3, not " + std::to_string(s->n_hidden) + served), -1;
+  bool f_known = false;
+  for (int id = 0; id < POL_SHAPE_COUNT; ++id) {
+    const PolShape t = pol_shape(id, s->lidar_channels);
+    if (t.F != s->features_dim) continue;
+    f_known = true;
+    bool same = t.n_hidden == s->n_hidden;
+    for (int i = 0; same && i < t.n_hidden; ++i) same = t.h[i] == s->hidden[i];
+    if (same) return id;
+  }
+  if (!f_known) return fail(who + "features_dim " + std::to_string(s->features_dim) + " is not served" + served), -1;
+  std::string h;
+  for (int i = 0; i < s->n_hidden; ++i) h += (i ? ", " : "") + std::to_string(s->hidden[i]);
+  return fail(who + "hidden [" + h + "] is not served with features_dim " + std::to_string(s->features_dim) + served), -1;
 }
 
 extern "C" {
@@ -1668,7 +1720,19 @@ __attribute__((visibility("default"))) int te_debug_stamps(te_env* e, uint64_t* 
 
 static int policy_words(int32_t lidar_channels, size_t* out) {
   if (lidar_channels != 2 && lidar_channels != 3) return fail("te_policy: lidar_channels must be 2 or 3");
-  *out = (size_t)policy_layout(lidar_channels).words;
+  *out = (size_t)policy_layout(pol_shape(POL_SHAPE_DEFAULT, lidar_channels)).words;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_shape_check(const te_policy_shape* shape) {
+  return policy_shape_id(shape, "te_policy_shape_check") < 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_param_words_shaped(const te_policy_shape* shape, size_t* out_words) {
+  if (!out_words) return fail("te_policy_param_words_shaped: null argument");
+  const int id = policy_shape_id(shape, "te_policy_param_words_shaped");
+  if (id < 0) return 1;
+  *out_words = (size_t)policy_layout(pol_shape(id, shape->lidar_channels)).words;
   return 0;
 }
 
@@ -1677,39 +1741,72 @@ __attribute__((visibility("default"))) int te_policy_param_words(int32_t lidar_c
   return policy_words(lidar_channels, out_words);
 }
 
+// te_policy_act and te_policy_act_shaped behind their shape checks (fn: the caller's name in the messages)
+static int policy_act(const char* fn, int shape_id, const float* params, int32_t lidar_channels, int32_t n, const float* lidar,
+                      const float* inertial, const float* last_action, const float* eps, float* mu, float* value, float* action, float* logp,
+                      float* action_env, void* stream) {
+  const std::string who = std::string(fn);
+  if (n <= 0) return fail(who + ": n must be positive");
+  if (!params || !lidar || !inertial || !last_action || !mu || !value) return fail(who + ": null argument");
+  if (eps && (!action || !logp || !action_env)) return fail(who + ": eps given, so action, logp and action_env must be too");
+  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
+  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)eps, (const void*)mu, (const void*)value,
+                        (const void*)action, (const void*)logp, (const void*)action_env})
+    if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
+  const PolicyIO io{lidar, inertial, last_action, eps, mu, value, eps ? action : nullptr, eps ? logp : nullptr, eps ? action_env : nullptr, n};
+  return policy_launch(kPolicyActKernels, shape_id, lidar_channels, params, n, stream, io);
+}
+
 __attribute__((visibility("default"))) int te_policy_act(const float* params, int32_t lidar_channels, int32_t n, const float* lidar,
                                                          const float* inertial, const float* last_action, const float* eps, float* mu,
                                                          float* value, float* action, float* logp, float* action_env, void* stream) {
   size_t words;
   if (policy_words(lidar_channels, &words)) return 1;
-  if (n <= 0) return fail("te_policy_act: n must be positive");
-  if (!params || !lidar || !inertial || !last_action || !mu || !value) return fail("te_policy_act: null argument");
-  if (eps && (!action || !logp || !action_env)) return fail("te_policy_act: eps given, so action, logp and action_env must be too");
-  if ((uintptr_t)params & 15) return fail("te_policy_act: params must be 16-byte aligned");
-  if ((uintptr_t)lidar & 7) return fail("te_policy_act: lidar must be 8-byte aligned");
-  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)eps, (const void*)mu, (const void*)value,
-                        (const void*)action, (const void*)logp, (const void*)action_env})
-    if ((uintptr_t)q & 3) return fail("te_policy_act: float arrays must be 4-byte aligned");
-  const PolicyIO io{lidar, inertial, last_action, eps, mu, value, eps ? action : nullptr, eps ? logp : nullptr, eps ? action_env : nullptr, n};
-  return policy_launch<&policy_act_kernel<2>, &policy_act_kernel<3>>(lidar_channels, params, n, stream, io);
+  return policy_act("te_policy_act", POL_SHAPE_DEFAULT, params, lidar_channels, n, lidar, inertial, last_action, eps, mu, value, action, logp,
+                    action_env, stream);
+}
+
+__attribute__((visibility("default"))) int te_policy_act_shaped(const float* params, const te_policy_shape* shape, int32_t n, const float* lidar,
+                                                                const float* inertial, const float* last_action, const float* eps, float* mu,
+                                                                float* value, float* action, float* logp, float* action_env, void* stream) {
+  const int id = policy_shape_id(shape, "te_policy_act_shaped");
+  if (id < 0) return 1;
+  return policy_act("te_policy_act_shaped", id, params, shape->lidar_channels, n, lidar, inertial, last_action, eps, mu, value, action, logp,
+                    action_env, stream);
+}
+
+// te_drive_wingman and te_drive_wingman_shaped behind their shape checks
+static int drive_wingman(const char* fn, int shape_id, te_env* e, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar,
+                         float* inertial, float* last_action, float* mu, void* stream) {
+  const std::string who = std::string(fn);
+  if (!wingman_is_callers(e, wingman))
+    return fail(who + ": this pursuer is not driven by the caller (exp05: cfg.ally_policy == TE_ALLY_EXTERNAL, pursuer 1; evaluation: the driver mask in cfg.evaluation)");
+  if (!params || !lidar || !inertial || !last_action) return fail(who + ": params, lidar, inertial and last_action are required");
+  if (lidar_channels != e->p.cfg.lidar_channels)
+    return fail(who + ": lidar_channels (" + std::to_string(lidar_channels) + ") differs from the env's cfg.lidar_channels (" +
+                std::to_string(e->p.cfg.lidar_channels) + ")");
+  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if (((uintptr_t)lidar & 15) || ((uintptr_t)last_action & 15)) return fail(who + ": lidar and last_action must be 16-byte aligned");
+  if (((uintptr_t)inertial & 3) || ((uintptr_t)mu & 3)) return fail(who + ": inertial and mu must be 4-byte aligned");
+  DeviceGuard guard(e->device);
+  if (te_observe_wingman(e, wingman, lidar, inertial, last_action, nullptr, stream)) return 1;
+  const PolicyIn in{lidar, inertial, last_action, nullptr, e->p.N};
+  return policy_launch(kPolicyDriveKernels, shape_id, lidar_channels, params, e->p.N, stream, in, e->p, (int)wingman, mu);
 }
 
 __attribute__((visibility("default"))) int te_drive_wingman(te_env* e, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar,
                                                             float* inertial, float* last_action, float* mu, void* stream) {
   if (!e) return fail("te_drive_wingman: null env");
-  if (!wingman_is_callers(e, wingman))
-    return fail("te_drive_wingman: this pursuer is not driven by the caller (exp05: cfg.ally_policy == TE_ALLY_EXTERNAL, pursuer 1; evaluation: the driver mask in cfg.evaluation)");
-  if (!params || !lidar || !inertial || !last_action) return fail("te_drive_wingman: params, lidar, inertial and last_action are required");
-  if (lidar_channels != e->p.cfg.lidar_channels)
-    return fail("te_drive_wingman: lidar_channels (" + std::to_string(lidar_channels) + ") differs from the env's cfg.lidar_channels (" +
-                std::to_string(e->p.cfg.lidar_channels) + ")");
-  if ((uintptr_t)params & 15) return fail("te_drive_wingman: params must be 16-byte aligned");
-  if (((uintptr_t)lidar & 15) || ((uintptr_t)last_action & 15)) return fail("te_drive_wingman: lidar and last_action must be 16-byte aligned");
-  if (((uintptr_t)inertial & 3) || ((uintptr_t)mu & 3)) return fail("te_drive_wingman: inertial and mu must be 4-byte aligned");
-  DeviceGuard guard(e->device);
-  if (te_observe_wingman(e, wingman, lidar, inertial, last_action, nullptr, stream)) return 1;
-  const PolicyIn in{lidar, inertial, last_action, nullptr, e->p.N};
-  return policy_launch<&policy_drive_kernel<2>, &policy_drive_kernel<3>>(lidar_channels, params, e->p.N, stream, in, e->p, (int)wingman, mu);
+  return drive_wingman("te_drive_wingman", POL_SHAPE_DEFAULT, e, wingman, params, lidar_channels, lidar, inertial, last_action, mu, stream);
+}
+
+__attribute__((visibility("default"))) int te_drive_wingman_shaped(te_env* e, int32_t wingman, const float* params, const te_policy_shape* shape,
+                                                                   float* lidar, float* inertial, float* last_action, float* mu, void* stream) {
+  if (!e) return fail("te_drive_wingman_shaped: null env");
+  const int id = policy_shape_id(shape, "te_drive_wingman_shaped");
+  if (id < 0) return 1;
+  return drive_wingman("te_drive_wingman_shaped", id, e, wingman, params, shape->lidar_channels, lidar, inertial, last_action, mu, stream);
 }
 
 // n up to 2^27: the conv1 layer's 12 * n reduction rows stay within int
@@ -1724,7 +1821,8 @@ static int policy_grad_check(int32_t lidar_channels, int32_t n, const char* fn) 
 __attribute__((visibility("default"))) int te_policy_grad_workspace_bytes(int32_t lidar_channels, int32_t n, size_t* out_bytes) {
   if (!out_bytes) return fail("te_policy_grad_workspace_bytes: null argument");
   if (policy_grad_check(lidar_channels, n, "te_policy_grad_workspace_bytes")) return 1;
-  *out_bytes = policy_grad_layout(lidar_channels, n, nullptr, policy_layout(lidar_channels), nullptr, nullptr, nullptr, nullptr);
+  const PolShape shape = pol_shape(POL_SHAPE_DEFAULT, lidar_channels);
+  *out_bytes = policy_grad_layout(shape, n, nullptr, policy_layout(shape), nullptr, nullptr, nullptr, nullptr);
   return 0;
 }
 
@@ -1745,7 +1843,8 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* param
                         (const void*)ret, (const void*)adv_mean_std, (const void*)stats})
     if ((uintptr_t)q & 3) return fail("te_policy_ppo_grad: float arrays must be 4-byte aligned");
   GradTileArgs t; GradPlan g;
-  const size_t need = policy_grad_layout(lidar_channels, n, static_cast<char*>(workspace), policy_layout(lidar_channels), grad, stats, &t, &g);
+  const PolShape shape = pol_shape(POL_SHAPE_DEFAULT, lidar_channels);
+  const size_t need = policy_grad_layout(shape, n, static_cast<char*>(workspace), policy_layout(shape), grad, stats, &t, &g);
   if (workspace_bytes < need)
     return fail("te_policy_ppo_grad: workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_policy_grad_workspace_bytes says " +
                 std::to_string(need) + ")");
@@ -1754,7 +1853,7 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* param
   t.clip = clip_range; t.vf_coef = vf_coef; t.ent_coef = ent_coef; t.inv_n = 1.f / (float)n;
   const PolicyIn in{lidar, inertial, last_action, index, n};
   const hipStream_t s = (hipStream_t)stream;
-  if (policy_launch<&policy_grad_tile_kernel<2>, &policy_grad_tile_kernel<3>>(lidar_channels, params, n, stream, in, t)) return 1;
+  if (policy_launch(kPolicyGradKernels, POL_SHAPE_DEFAULT, lidar_channels, params, n, stream, in, t)) return 1;
   hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);

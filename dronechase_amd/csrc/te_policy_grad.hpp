@@ -25,7 +25,7 @@ constexpr int kGradSlice = 2048;      // rows (of a layer's reduction) per split
 constexpr int kGradTile = 64;         // output tile of policy_wgrad_kernel: 64 x 64, four waves of 32 x 32
 constexpr int kGradStep = 32;         // rows staged in LDS per step
 constexpr int kGradLS = kGradStep + 4;
-constexpr int kGradLayers = 17;       // 15 weight layers, log_std, the statistics
+constexpr int kGradLayers = 19;       // 17 weight layers (two of them empty in the default shape), log_std, the statistics
 static_assert(kGradLayers == POL_L_COUNT, "one split-K layer per row of pol_layer's table");
 
 // One layer of the split-K reduction: partial[slice][N][K + 1] of dZ[R][N]^T [X[R][K] | 1].  Row counts R are multiples of 32.
@@ -74,7 +74,7 @@ TE_DEV auto pol_wT(const float* __restrict__ W) {
 // read, of L's shape; a constant once the caller's loop is unrolled.)
 template <int L, int C, class Epi>
 TE_DEV void pol_linear_back(const PolicyParams& P, const float* dZ, int ld, Epi epi, int l = L) {
-  constexpr PolLayer y = pol_layer(L, C);
+  constexpr PolLayer y = pol_layer(L, pol_shape(POL_SHAPE_DEFAULT, C));
   pol_gemm<y.N, y.K>(dZ, ld, pol_wT<y.K>(P.base + P.at[l].w), [](int) { return 0.f; }, epi);
 }
 
@@ -193,12 +193,13 @@ __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyPar
   __syncthreads();
 
   // ---- the inertial and last_action MLPs: down to the first layer's dZ (their inputs need no gradient)
-  constexpr auto same = [](int a, int b) { return pol_layer(a, C).N == pol_layer(b, C).N && pol_layer(a, C).K == pol_layer(b, C).K; };
+  constexpr auto layer = [](int l) { return pol_layer(l, pol_shape(POL_SHAPE_DEFAULT, C)); };
+  constexpr auto same = [=](int a, int b) { return layer(a).N == layer(b).N && layer(a).K == layer(b).K; };
   static_assert(same(POL_L_IN1, POL_L_AC1) && same(POL_L_IN2, POL_L_AC2), "the two chains' hidden layers have one shape");
 #pragma unroll
   for (int chain = 0; chain < 2; ++chain) {   // unrolled: l0, and with it every index into P and g, is a compile-time constant
     const int l0 = chain ? POL_L_AC0 : POL_L_IN0;
-    const int sv1 = pol_layer(l0 + 1, C).x, sv2 = pol_layer(l0 + 2, C).x;
+    const int sv1 = layer(l0 + 1).x, sv2 = layer(l0 + 2).x;
     pol_linear_back<POL_L_IN2, C>(P, DZ + 192 + 128 * chain, kPolZS, [&](int m, int n, float v) {
       const float d = at(sv2, m, 0, n) > 0.f ? v : 0.f;
       T1[m * kPolTS + n] = d;
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyPar
 // The workspace of te_policy_ppo_grad for n rows (Bp = n rounded up to the tile): every layer's input X [R][K] and pre-activation
 // gradient dZ [R][N] row-major, R = Bp x the layer's positions, then the split-K partials, in the order of the take() calls.  Host
 // only.  With ws == NULL only the size is computed; otherwise the tile kernel's pointers and the split-K plan are filled in.
-inline size_t policy_grad_layout(int C, int n, char* ws, const PolicyParams& P, float* grad, float* stats, GradTileArgs* ta, GradPlan* gp) {
+inline size_t policy_grad_layout(PolShape S, int n, char* ws, const PolicyParams& P, float* grad, float* stats, GradTileArgs* ta, GradPlan* gp) {
   const size_t Bp = ((size_t)n + kPolTileM - 1) / kPolTileM * kPolTileM;
   size_t off = 0;
   auto take = [&](size_t rows, int cols) {
@@ -239,13 +240,13 @@ inline size_t policy_grad_layout(int C, int n, char* ws, const PolicyParams& P, 
     return at;
   };
   GradTileArgs t{};
-  for (int l = 0; l < POL_L_WEIGHTS; ++l) { const PolLayer y = pol_layer(l, C); t.save_pos[y.x] = y.pos; t.save_ld[y.x] = y.K; }
+  for (int l = 0; l < POL_L_WEIGHTS; ++l) { const PolLayer y = pol_layer(l, S); t.save_pos[y.x] = y.pos; t.save_ld[y.x] = y.K; }
   for (int sv = 0; sv < POL_SV_COUNT; ++sv) t.save[sv] = take(Bp * t.save_pos[sv], t.save_ld[sv]);
-  for (int l = 0; l < POL_L_COUNT; ++l) t.dz[l] = take(Bp * pol_layer(l, C).pos, pol_layer(l, C).N);
+  for (int l = 0; l < POL_L_COUNT; ++l) t.dz[l] = take(Bp * pol_layer(l, S).pos, pol_layer(l, S).N);
 
   GradPlan g{};
   for (int l = 0; l < kGradLayers; ++l) {
-    const PolLayer y = pol_layer(l, C);
+    const PolLayer y = pol_layer(l, S);
     GradLayer& L = g.L[l];
     L.dz = t.dz[l];
     L.x = l < POL_L_WEIGHTS ? t.save[y.x] : nullptr;

@@ -172,13 +172,14 @@ __global__ __launch_bounds__(256) void set_ally_actions_kernel(Params p, int me,
 // read as te_policy_act reads its rows), then set_ally_actions_kernel's drive with the clamped mean.  pol_forward is the one
 // policy_act_kernel runs, so mu is bitwise te_policy_act's.  Every row is computed; rows of envs whose pursuer is dead keep
 // their state (the reference does not call predict for them), mu is written for all rows.
-template <int C>
+template <int C, int S = POL_SHAPE_DEFAULT>
 __global__ __launch_bounds__(kPolThreads) void policy_drive_kernel(PolicyParams P, PolicyIn in, Params p, int me, float* __restrict__ mu) {
   extern __shared__ __attribute__((aligned(16))) float pol_lds[];
-  const int tid = threadIdx.x, env = blockIdx.x * kPolTileM + tid;
-  pol_forward<C>(P, in, pol_lds, blockIdx.x * kPolTileM, PolNoSave{});
-  if (tid >= kPolTileM || env >= in.n) return;
-  const float* MU = pol_mu_lds(pol_lds) + tid * 4;   // read back by the thread that computed it
+  constexpr int M = pol_lds_plan(pol_shape(S, C)).M;
+  const int tid = threadIdx.x, env = blockIdx.x * M + tid;
+  pol_forward<C, S>(P, in, pol_lds, blockIdx.x * M, PolNoSave{});
+  if (tid >= M || env >= in.n) return;
+  const float* MU = pol_mu_lds<S>(pol_lds) + tid * 4;   // read back by the thread that computed it
   if (mu) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) mu[(size_t)env * 4 + a] = MU[a];

@@ -9,8 +9,9 @@ envs is 34 GB of observations — 288 GB per MI355X is what makes that layout po
 autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the HIP kernels of libthreatengage.so.
 
   * topology = the reference's extractor: LIDAR conv(k4,s4,32) -> conv(k2,s2,64) -> flatten; inertial and
-    last_action 3 x Linear(128); concat -> Linear(256); then SB3's default pi / vf heads (2 x 64, tanh) and a
-    state-independent log-std (stable_baselines3 ActorCriticPolicy defaults);
+    last_action 3 x Linear(128); concat -> Linear(features_dim); then pi / vf heads of net_arch widths with tanh (SB3's default
+    2 x 64 and features_dim 256 unless told otherwise; the reference's trained networks are features_dim 512 with net_arch
+    (128, 256, 512) or (512, 128, 256): load_sb3_policy below reads their checkpoints) and a state-independent log-std;
   * losses / GAE = the PPO of Schulman et al. 2017 with SB3's defaults (clip 0.2, gae_lambda 0.95, gamma 0.99,
     vf_coef 0.5, ent_coef 0, max_grad_norm 0.5, advantage normalisation per minibatch, 10 epochs);
   * PPOConfig.fused_forward: the rollout's forward, sampling and log-prob in one HIP launch (te_policy_act, FusedPolicy below)
@@ -33,7 +34,7 @@ from __future__ import annotations
 
 import copy
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import ctypes as C
 
@@ -44,10 +45,14 @@ from . import _lib
 
 
 class LidarInertialActionPolicy(nn.Module):
-    """Actor-critic over {"lidar" [B,C,13,26], "inertial_data" [B,15], "last_action" [B,4]}."""
+    """Actor-critic over {"lidar" [B,C,13,26], "inertial_data" [B,15], "last_action" [B,4]}.  net_arch: the widths of the 1-3 hidden
+    layers (Linear + Tanh each) of the pi head and of the vf head, the reference's net_arch=dict(pi=hiddens, vf=hiddens)."""
 
-    def __init__(self, lidar_shape=(3, 13, 26), inertial_dim: int = 15, action_dim: int = 4, features_dim: int = 256):
+    def __init__(self, lidar_shape=(3, 13, 26), inertial_dim: int = 15, action_dim: int = 4, features_dim: int = 256, net_arch=(64, 64)):
         super().__init__()
+        net_arch = tuple(int(w) for w in net_arch)
+        if not 1 <= len(net_arch) <= 3 or min(net_arch) < 1:
+            raise ValueError(f"LidarInertialActionPolicy: net_arch must be 1 to 3 positive widths, not {net_arch}")
         c = lidar_shape[0]
         self.lidar = nn.Sequential(nn.Conv2d(c, 32, kernel_size=4, stride=4), nn.ReLU(),
                                    nn.Conv2d(32, 64, kernel_size=2, stride=2), nn.ReLU(), nn.Flatten())
@@ -59,10 +64,14 @@ class LidarInertialActionPolicy(nn.Module):
 
         self.inertial, self.action = mlp(inertial_dim), mlp(action_dim)
         self.final = nn.Sequential(nn.Linear(n_lidar + 256, features_dim), nn.ReLU())
-        self.pi = nn.Sequential(nn.Linear(features_dim, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh())
-        self.vf = nn.Sequential(nn.Linear(features_dim, 64), nn.Tanh(), nn.Linear(64, 64), nn.Tanh())
-        self.mu = nn.Linear(64, action_dim)
-        self.value = nn.Linear(64, 1)
+
+        def head():
+            widths = (features_dim,) + net_arch
+            return nn.Sequential(*(m for a, b in zip(widths, widths[1:]) for m in (nn.Linear(a, b), nn.Tanh())))
+
+        self.pi, self.vf = head(), head()
+        self.mu = nn.Linear(net_arch[-1], action_dim)
+        self.value = nn.Linear(net_arch[-1], 1)
         self.log_std = nn.Parameter(torch.zeros(action_dim))
 
     def features(self, obs: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -93,10 +102,114 @@ def pack_policy(policy: nn.Module, out: Optional[torch.Tensor] = None) -> torch.
     return torch.cat(flat) if out is None else torch.cat(flat, out=out)
 
 
-def policy_param_words(lidar_channels: int) -> int:
+DEFAULT_FEATURES_DIM, DEFAULT_NET_ARCH = 256, (64, 64)
+
+
+def policy_shape(policy: nn.Module) -> Tuple[int, int, Tuple[int, ...]]:
+    """(lidar_channels, features_dim, net_arch) read from a LidarInertialActionPolicy's layers."""
+    return (int(policy.lidar[0].in_channels), int(policy.final[0].out_features),
+            tuple(int(m.out_features) for m in policy.pi if isinstance(m, nn.Linear)))
+
+
+def _c_shape(lidar_channels: int, features_dim: int, net_arch) -> "_lib.PolicyShape":
+    net_arch = tuple(int(w) for w in net_arch)
+    # more than 3 widths cannot be written into the struct's 4 slots in full: n_hidden alone carries the count, and the check refuses it
+    return _lib.PolicyShape(int(lidar_channels), int(features_dim), len(net_arch), (C.c_int32 * 4)(*(net_arch[:4])))
+
+
+def check_policy_shape(lidar_channels: int, features_dim: int = DEFAULT_FEATURES_DIM, net_arch=DEFAULT_NET_ARCH) -> "_lib.PolicyShape":
+    """The te_policy_shape of a shape the HIP kernels serve; a ValueError that lists the served shapes otherwise."""
+    shape = _c_shape(lidar_channels, features_dim, net_arch)
+    lib = _lib.load()
+    if lib.te_policy_shape_check(C.byref(shape)) != 0:
+        raise ValueError(lib.te_last_error().decode())
+    return shape
+
+
+def is_default_shape(features_dim: int, net_arch) -> bool:
+    return int(features_dim) == DEFAULT_FEATURES_DIM and tuple(int(w) for w in net_arch) == DEFAULT_NET_ARCH
+
+
+def policy_param_words(lidar_channels: int, features_dim: int = DEFAULT_FEATURES_DIM, net_arch=DEFAULT_NET_ARCH) -> int:
+    """The words of the packed parameter buffer of a served shape (te_policy_param_words_shaped)."""
+    shape = check_policy_shape(lidar_channels, features_dim, net_arch)
     out = C.c_size_t()
-    _lib.check(_lib.load().te_policy_param_words(int(lidar_channels), C.byref(out)), "te_policy_param_words")
+    _lib.check(_lib.load().te_policy_param_words_shaped(C.byref(shape), C.byref(out)), "te_policy_param_words_shaped")
     return int(out.value)
+
+
+# SB3's MultiInputPolicy names (stable-baselines3's ActorCriticPolicy; the extractor's attributes are the reference's,
+# ppo_policies.py:245-256) -> this module's.  Taken from SB3's documentation, not checked against a checkpoint file.
+_SB3_EXTRACTOR = {"lidar_feature_extractor": "lidar", "inertial_feature_extractor": "inertial", "action_feature_extractor": "action",
+                  "final_layer": "final"}
+_SB3_PREFIX = {"mlp_extractor.policy_net.": "pi.", "mlp_extractor.value_net.": "vf.", "action_net.": "mu.", "value_net.": "value."}
+
+
+def _sb3_key(key: str) -> Optional[str]:
+    """The module's name of SB3 state-dict key `key`; None for a key the module has no counterpart of."""
+    if key == "log_std":
+        return key
+    if key.startswith("features_extractor."):
+        attr, _, rest = key[len("features_extractor."):].partition(".")
+        return f"{_SB3_EXTRACTOR[attr]}.{rest}" if attr in _SB3_EXTRACTOR and rest else None
+    for pre, ours in _SB3_PREFIX.items():
+        if key.startswith(pre):
+            return ours + key[len(pre):]
+    return None
+
+
+def load_sb3_policy(path_or_state_dict, lidar_shape=(3, 13, 26)) -> LidarInertialActionPolicy:
+    """A LidarInertialActionPolicy with the weights of an SB3 MultiInputPolicy checkpoint of the reference's extractor, without
+    stable-baselines3: `path_or_state_dict` is the model's .zip (its policy.pth is read with torch.load(weights_only=True)) or the
+    policy's state dict.  features_dim and net_arch are inferred from the tensors' shapes.  SB3 stores the extractor three times when
+    it is shared (features_extractor, pi_features_extractor, vf_features_extractor): the copies must equal features_extractor's.
+    Any other unknown key, and any key the module needs and the checkpoint lacks, is a KeyError naming it."""
+    sd = path_or_state_dict
+    if not isinstance(sd, dict):
+        import io
+        import zipfile
+        with zipfile.ZipFile(sd) as z:
+            sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
+    mapped: Dict[str, torch.Tensor] = {}
+    for key, t in sd.items():
+        dup = next((d for d in ("pi_features_extractor.", "vf_features_extractor.") if key.startswith(d)), None)
+        if dup is not None:
+            shared = "features_extractor." + key[len(dup):]
+            if _sb3_key(shared) is None:
+                raise KeyError(f"load_sb3_policy: unknown key {key!r}")
+            if shared in sd and not torch.equal(sd[shared], t):
+                raise ValueError(f"load_sb3_policy: {key!r} differs from {shared!r}: the extractor is not shared, which this policy cannot express")
+            if shared in sd:
+                continue
+            key = shared
+        name = _sb3_key(key)
+        if name is None:
+            raise KeyError(f"load_sb3_policy: unknown key {key!r}")
+        mapped[name] = t
+    for need in ("final.0.weight", "pi.0.weight"):
+        if need not in mapped:
+            back = {"final.0.weight": "features_extractor.final_layer.0.weight", "pi.0.weight": "mlp_extractor.policy_net.0.weight"}[need]
+            raise KeyError(f"load_sb3_policy: missing key {back!r}")
+    net_arch = []
+    while len(net_arch) < 3 and f"pi.{2 * len(net_arch)}.weight" in mapped:
+        net_arch.append(int(mapped[f"pi.{2 * len(net_arch)}.weight"].shape[0]))
+    policy = LidarInertialActionPolicy(lidar_shape=tuple(lidar_shape), features_dim=int(mapped["final.0.weight"].shape[0]), net_arch=tuple(net_arch))
+    ours = policy.state_dict()
+    back = {_sb3_key(k): k for k in sd if _sb3_key(k) is not None}
+    for name in mapped:
+        if name not in ours:
+            raise KeyError(f"load_sb3_policy: unknown key {back.get(name, name)!r}")
+    for name, t in ours.items():
+        if name not in mapped:
+            inv = {v: k for k, v in _SB3_EXTRACTOR.items()}
+            head, _, rest = name.partition(".")
+            sb3 = (f"features_extractor.{inv[head]}.{rest}" if head in inv else
+                   next((pre + rest for pre, o in _SB3_PREFIX.items() if o == head + "."), name))
+            raise KeyError(f"load_sb3_policy: missing key {sb3!r}")
+        if tuple(mapped[name].shape) != tuple(t.shape):
+            raise ValueError(f"load_sb3_policy: {back.get(name, name)!r} has shape {tuple(mapped[name].shape)}, the module's {name} {tuple(t.shape)}")
+    policy.load_state_dict({k: mapped[k].float() for k in ours})
+    return policy
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -109,21 +222,28 @@ def require_f32(who: str, name: str, t: torch.Tensor, shape, device: torch.devic
         raise ValueError(f"{who}: {name} must be a contiguous float32 {shown or shape} tensor on {device}")
 
 
+GRAD_DEFAULT_ONLY = ("the gradient kernel te_policy_ppo_grad serves the default shape only (features_dim 256, net_arch (64, 64)): "
+                     "PPOConfig.fused_update and fused_optimizer are not available for this policy; without them update() runs autograd")
+
+
 class FusedPolicy:
-    """Inference of a LidarInertialActionPolicy by te_policy_act: the forward pass, the Gaussian sample, its log-prob and the
-    clamp of the action in one HIP launch.  The weights are packed into ONE device buffer that keeps its address for the life of
+    """Inference of a LidarInertialActionPolicy by te_policy_act_shaped: the forward pass, the Gaussian sample, its log-prob and the
+    clamp of the action in one HIP launch, for every shape the kernels serve (features_dim 256 with net_arch (64, 64); features_dim
+    512 with (128, 256, 512) or (512, 128, 256)); any other shape is a ValueError that lists them.  The weights are packed into ONE device buffer that keeps its address for the life of
     this object; refresh() repacks the module's current weights into it in place, so a HIP graph that captured a call sees them.
     Call refresh() after every change of the module's weights (PPO does, at the start of every collect()).
     After bind_parameters() the module's parameters are views of the packed buffer and there is nothing left to repack."""
 
     def __init__(self, policy: nn.Module):
         self.policy = policy
-        self.lidar_channels = int(policy.lidar[0].in_channels)
+        self.lidar_channels, self.features_dim, self.net_arch = policy_shape(policy)
         params = _packed_order(policy)
         self.device = params[0].device
         if self.device.type != "cuda":
             raise ValueError("FusedPolicy runs the HIP kernel te_policy_act: the policy must live on a GPU")
-        words = policy_param_words(self.lidar_channels)
+        self.shape = check_policy_shape(self.lidar_channels, self.features_dim, self.net_arch)    # the te_policy_shape of every call
+        self.default_shape = is_default_shape(self.features_dim, self.net_arch)
+        words = policy_param_words(self.lidar_channels, self.features_dim, self.net_arch)
         if sum(p.numel() for p in params) != words:
             raise ValueError(f"policy has {sum(p.numel() for p in params)} parameters, te_policy_act's layout {words}: not a LidarInertialActionPolicy")
         self.params = torch.empty(words, dtype=torch.float32, device=self.device)
@@ -173,6 +293,8 @@ class FusedPolicy:
         advantage; None uses it as it is.  One te_policy_ppo_grad call: three launches, no host synchronisation.  The
         workspace (~17.5 KB per row) is owned here and grows on demand, which a capturing stream does not allow: make the first
         call of a size outside capture."""
+        if not self.default_shape:
+            raise ValueError(GRAD_DEFAULT_ONLY)
         lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
         m = lidar.shape[0]
         b = m if index is None else index.shape[0]
@@ -215,8 +337,8 @@ class FusedPolicy:
                 require_f32("FusedPolicy", name, t, shape, self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(_lib.load().te_policy_act(self.params.data_ptr(), self.lidar_channels, n, lidar.data_ptr(), inertial.data_ptr(),
-                                                 last_action.data_ptr(), _ptr(eps), *(_ptr(o) for o in outs), stream), "te_policy_act")
+            _lib.check(_lib.load().te_policy_act_shaped(self.params.data_ptr(), C.byref(self.shape), n, lidar.data_ptr(), inertial.data_ptr(),
+                                                        last_action.data_ptr(), _ptr(eps), *(_ptr(o) for o in outs), stream), "te_policy_act_shaped")
 
     def forward(self, obs: Dict[str, torch.Tensor]):
         """(mu [N, 4], value [N]) of the module's forward."""
@@ -356,6 +478,9 @@ class PPOConfig:
     # collect() and the bootstrap value: the policy's forward + sampling + log-prob + clamp as ONE HIP launch (te_policy_act, FusedPolicy)
     # instead of the op-by-op PyTorch forward; eps still comes from torch.randn_like, update() still runs the PyTorch module.
     # Off by default: the outputs agree with the module's to ~1.5e-7 (measured), not bit for bit (another summation order)
+    # It serves the shapes FusedPolicy lists, and pays for the default shape only: at 65 536 rows the launch takes 0.56 ms against PyTorch's
+    # 1.14 ms for the default, but 3.06 against 1.84 ms for features_dim 512 with net_arch (128, 256, 512) and 3.83 against 2.04 ms with
+    # (512, 128, 256) (measured, DESIGN.md 7, profiles/policy_shapes.json): for those, leave it off unless the single launch matters more
     fused_forward: bool = False
     # update(): the minibatch's loss gradient in ONE ABI call (te_policy_ppo_grad, FusedPolicy.ppo_grad: forward, loss, backward and
     # deterministic split-K weight gradients in HIP, the rows read through the minibatch index) instead of the PyTorch forward +
@@ -390,6 +515,11 @@ class PPOConfig:
     # over the rollout (SB3's logger key; NaN when Var(ret) is 0), from two more te_adv_stats calls; with several GPUs it is rank-local
     # (each rank's own rollout; no collective).  Needs a GPU, not fused_update.  Off by default: every dict, tensor and launch is unchanged
     fused_advantages: bool = False
+    # the shape of the policy PPO builds when it is given none: the trunk's width and the widths of the pi / vf heads' hidden layers
+    # (LidarInertialActionPolicy).  The reference's trained networks are features_dim=512 with net_arch=(128, 256, 512) or (512, 128, 256).
+    # fused_update and fused_optimizer serve the default shape only
+    features_dim: int = 256
+    net_arch: tuple = (64, 64)
 
     def __post_init__(self):
         if self.fused_optimizer and not self.fused_update:
@@ -482,7 +612,10 @@ class PPO:
             if int(self.cfg.wingman_sync_every) < 1:
                 raise ValueError("PPOConfig.wingman_sync_every must be >= 1")
         torch.manual_seed(seed)
-        self.policy = (policy or LidarInertialActionPolicy(lidar_shape=tuple(env.lidar.shape[1:]))).to(self.device)
+        self.policy = (policy or LidarInertialActionPolicy(lidar_shape=tuple(env.lidar.shape[1:]), features_dim=self.cfg.features_dim,
+                                                           net_arch=self.cfg.net_arch)).to(self.device)
+        if (self.cfg.fused_update or self.cfg.fused_optimizer) and not is_default_shape(*policy_shape(self.policy)[1:]):
+            raise ValueError(GRAD_DEFAULT_ONLY)
         fused = bool(self.cfg.fast_learner) and self.device.type == "cuda"
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=self.cfg.learning_rate, eps=1e-5, **({"fused": True} if fused else {}))
         shapes = {"lidar": tuple(env.lidar.shape[1:]), "inertial_data": (env.inertial.shape[1],), "last_action": (4,)}

@@ -3,6 +3,7 @@
 
     python examples/ppo_stage03.py --envs 65536 --iters 5
     python examples/ppo_stage03.py --envs 8192 --episode-stats --eval-episodes 200
+    python examples/ppo_stage03.py --envs 8192 --features-dim 512 --net-arch 128,256,512 --fused-forward    # the reference's trained shape
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/ppo_stage03.py --envs 8192
 
 One process per GPU; each rank owns `--envs` environments (RNG keyed on the global env index) and the gradient
@@ -25,6 +26,10 @@ def main():
     ap.add_argument("--task", default="stage03")
     ap.add_argument("--episode-stats", action="store_true", help="log ep_rew_mean, ep_len_mean, ... of the episodes that finished in each collect (rank-local)")
     ap.add_argument("--eval-episodes", type=int, default=0, help="after training: evaluate the policy over N episodes on a fresh env (rank 0)")
+    ap.add_argument("--features-dim", type=int, default=256, help="width of the policy's trunk (the reference trains 512)")
+    ap.add_argument("--net-arch", type=lambda s: tuple(int(w) for w in s.split(",")), default=(64, 64),
+                    help="widths of the pi / vf heads' hidden layers, e.g. 128,256,512 (the reference's h[128, 256, 512] checkpoints)")
+    ap.add_argument("--fused-forward", action="store_true", help="the rollout's policy forward as one HIP launch (PPOConfig.fused_forward)")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -45,7 +50,8 @@ def main():
         else:
             dist.init_process_group(backend)
     env = BatchedEnv(default_config(args.task, n_envs=args.envs, env_index_base=rank * args.envs), dev)
-    ppo = PPO(env, PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, n_epochs=args.epochs, episode_stats=args.episode_stats), seed=0)
+    ppo = PPO(env, PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, n_epochs=args.epochs, episode_stats=args.episode_stats,
+                             features_dim=args.features_dim, net_arch=args.net_arch, fused_forward=args.fused_forward), seed=0)
     if rank == 0:
         print(f"rollout buffer {ppo.buf.bytes() / 2**30:.1f} GiB on {dev}; policy parameters {sum(p.numel() for p in ppo.policy.parameters())}", flush=True)
     for it in range(args.iters):

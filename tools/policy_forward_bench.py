@@ -1,22 +1,43 @@
 #!/usr/bin/env python3
 """The policy's inference: PyTorch's op-by-op forward + sampling against te_policy_act (one launch, te_policy.hpp) at 8 192, 16 384 and
 65 536 rows, then the PPO collect split (tools/ppo_split.py's way) with PPOConfig.fused_forward off and on.  One JSON document on stdout.
-    python tools/policy_forward_bench.py [n_envs_for_collect] [n_steps]
-Bound: 267 k MACs per row -> 65 536 rows = 35.0 GFLOP = 0.22 ms at the 157.3 TF fp32 MFMA peak."""
+    python tools/policy_forward_bench.py [n_envs_for_collect] [n_steps] [--features-dim F] [--net-arch 128,256,512] [--no-collect]
+--features-dim / --net-arch: the shape of the policy of those two parts (default 256 and 64,64).
+Then every served shape at 65 536 rows: the fused launch (forward only, FusedPolicy.forward) against the op-by-op PyTorch forward of
+the same module, five alternating repeats each (median, min and max), written to profiles/policy_shapes.json as well.
+Bound, default shape: 267 k MACs per row -> 65 536 rows = 35.0 GFLOP = 0.22 ms at the 157.3 TF fp32 MFMA peak."""
+import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import torch
 from dronechase_amd import default_config
 from dronechase_amd.batched_env import BatchedEnv
 from dronechase_amd.ppo import PPO, FusedPolicy, LidarInertialActionPolicy, PPOConfig
 
-N_COLLECT = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-T = int(sys.argv[2]) if len(sys.argv) > 2 else 32
-MACS_PER_ROW = 32 * 48 * 12 + 64 * 128 * 3 + (15 * 128 + 2 * 128 * 128) + (4 * 128 + 2 * 128 * 128) + 448 * 256 + 2 * (256 * 64 + 64 * 64) + 64 * 5
+ap = argparse.ArgumentParser()
+ap.add_argument("n_collect", nargs="?", type=int, default=65536)
+ap.add_argument("n_steps", nargs="?", type=int, default=32)
+ap.add_argument("--features-dim", type=int, default=256)
+ap.add_argument("--net-arch", type=lambda s: tuple(int(w) for w in s.split(",")), default=(64, 64))
+ap.add_argument("--no-collect", action="store_true", help="skip the PPO collect split")
+args = ap.parse_args()
+N_COLLECT, T = args.n_collect, args.n_steps
+SERVED = {"default": (256, (64, 64)), "reference BO": (512, (128, 256, 512)), "reference learn": (512, (512, 128, 256))}
+
+
+def macs_per_row(features_dim, net_arch, c=3):
+    widths = (features_dim,) + tuple(net_arch)
+    return 32 * 16 * c * 12 + 64 * 128 * 3 + (15 * 128 + 2 * 128 * 128) + (4 * 128 + 2 * 128 * 128) + 448 * features_dim + \
+        2 * sum(a * b for a, b in zip(widths, widths[1:])) + net_arch[-1] * 5
+
+
+MACS_PER_ROW = macs_per_row(args.features_dim, args.net_arch)
 PEAK_TFLOPS = 157.3
 
 
@@ -28,9 +49,9 @@ def timed(fn, reps):
     return (time.perf_counter() - t) / reps
 
 
-out = {"macs_per_row": MACS_PER_ROW, "forward": []}
+out = {"features_dim": args.features_dim, "net_arch": list(args.net_arch), "macs_per_row": MACS_PER_ROW, "forward": []}
 torch.manual_seed(0)
-policy = LidarInertialActionPolicy().to("cuda:0")
+policy = LidarInertialActionPolicy(features_dim=args.features_dim, net_arch=args.net_arch).to("cuda:0")
 fused = FusedPolicy(policy)
 for n in (8192, 16384, 65536):
     obs = {"lidar": torch.rand(n, 3, 13, 26, device="cuda:0"), "inertial_data": torch.rand(n, 15, device="cuda:0") * 2 - 1,
@@ -57,6 +78,46 @@ for n in (8192, 16384, 65536):
 del fused, policy
 torch.cuda.empty_cache()
 
+# ---- every served shape at 65 536 rows: the fused launch against the PyTorch forward it replaces, alternating repeats
+ROWS, REPEATS = 65536, 5
+shapes = {"rows": ROWS, "repeats": REPEATS, "peak_fp32_mfma_TFLOPS": PEAK_TFLOPS, "shapes": []}
+obs = {"lidar": torch.rand(ROWS, 3, 13, 26, device="cuda:0"), "inertial_data": torch.rand(ROWS, 15, device="cuda:0") * 2 - 1,
+       "last_action": torch.rand(ROWS, 4, device="cuda:0")}
+for name, (fdim, arch) in SERVED.items():
+    torch.manual_seed(0)
+    policy = LidarInertialActionPolicy(features_dim=fdim, net_arch=arch).to("cuda:0")
+    fused = FusedPolicy(policy)
+
+    @torch.no_grad()
+    def torch_forward():
+        return policy(obs)
+
+    for _ in range(5):
+        torch_forward(); fused.forward(obs)
+    t_f, t_t = [], []
+    for _ in range(REPEATS):
+        t_f.append(timed(lambda: fused.forward(obs), 100) * 1e3)
+        t_t.append(timed(torch_forward, 30) * 1e3)
+    flop = 2.0 * macs_per_row(fdim, arch) * ROWS
+    med_f, med_t = statistics.median(t_f), statistics.median(t_t)
+    shapes["shapes"].append({
+        "name": name, "features_dim": fdim, "net_arch": list(arch), "param_words": fused.params.numel(), "macs_per_row": macs_per_row(fdim, arch),
+        "fused_forward_ms": {"median": med_f, "min": min(t_f), "max": max(t_f)},
+        "pytorch_forward_ms": {"median": med_t, "min": min(t_t), "max": max(t_t)},
+        "pytorch_over_fused": med_t / med_f, "fused_TFLOPS": flop / med_f / 1e9,
+        "fused_fraction_of_fp32_mfma_peak": flop / med_f / 1e9 / PEAK_TFLOPS, "bound_ms": flop / (PEAK_TFLOPS * 1e12) * 1e3})
+    del fused, policy
+del obs
+torch.cuda.empty_cache()
+out["shapes"] = shapes
+with open(os.path.join(ROOT, "profiles", "policy_shapes.json"), "w") as f:
+    json.dump(shapes, f, indent=1)
+    f.write("\n")
+
+if args.no_collect:
+    print(json.dumps(out, indent=1))
+    sys.exit(0)
+
 env = BatchedEnv(default_config("stage03", n_envs=N_COLLECT), "cuda:0")
 env.reset()
 a = env.random_actions(1, 0)
@@ -67,7 +128,8 @@ env.close()
 out["collect"] = {"n_envs": N_COLLECT, "n_steps": T, "env_step_us": t_env * 1e6}
 for ff in (False, True):
     env = BatchedEnv(default_config("stage03", n_envs=N_COLLECT), "cuda:0")
-    ppo = PPO(env, PPOConfig(n_steps=T, batch_size=N_COLLECT, n_epochs=1, use_graph=True, fused_forward=ff), seed=3)
+    ppo = PPO(env, PPOConfig(n_steps=T, batch_size=N_COLLECT, n_epochs=1, use_graph=True, fused_forward=ff, features_dim=args.features_dim,
+                             net_arch=args.net_arch), seed=3)
     ppo.collect()                          # graph capture
     t_col = timed(ppo.collect, 3)
     out["collect"]["fused_forward" if ff else "pytorch_forward"] = {
