@@ -1084,13 +1084,13 @@ static int policy_launch(PolKernel<Args...> const (&ks)[NS][2], int shape_id, in
   return 0;
 }
 
-// every served instance of an inference kernel template K<C, shape id>
+// every served instance of a policy kernel template K<C, shape id>
 #define TE_POL_INSTANCES(K) \
   {{&K<2, POL_SHAPE_DEFAULT>, &K<3, POL_SHAPE_DEFAULT>}, {&K<2, POL_SHAPE_BO>, &K<3, POL_SHAPE_BO>}, {&K<2, POL_SHAPE_LEARN>, &K<3, POL_SHAPE_LEARN>}}
 static_assert(POL_SHAPE_COUNT == 3, "TE_POL_INSTANCES lists every shape");
 static const PolKernel<PolicyIO> kPolicyActKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_act_kernel);
 static const PolKernel<PolicyIn, Params, int, float*> kPolicyDriveKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_drive_kernel);
-static const PolKernel<PolicyIn, GradTileArgs> kPolicyGradKernels[1][2] = {{&policy_grad_tile_kernel<2>, &policy_grad_tile_kernel<3>}};
+static const PolKernel<PolicyIn, GradTileArgs> kPolicyGradKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_grad_tile_kernel);
 
 static std::string shape_text(const PolShape& s) {
   std::string t = "features_dim " + std::to_string(s.F) + ", hidden";
@@ -1809,21 +1809,69 @@ __attribute__((visibility("default"))) int te_drive_wingman_shaped(te_env* e, in
   return drive_wingman("te_drive_wingman_shaped", id, e, wingman, params, shape->lidar_channels, lidar, inertial, last_action, mu, stream);
 }
 
-// n up to 2^27: the conv1 layer's 12 * n reduction rows stay within int
-static int policy_grad_check(int32_t lidar_channels, int32_t n, const char* fn) {
-  size_t words;
-  if (policy_words(lidar_channels, &words)) return 1;
-  if (n <= 0) return fail(std::string(fn) + ": n must be positive");
-  if (n > (1 << 27)) return fail(std::string(fn) + ": n must be at most 2^27");
+// The gradient entries behind their shape checks (fn: the caller's name in the messages; size_fn: the entry that tells the workspace's
+// size).  n up to 2^27: the conv1 layer's 12 * n reduction rows stay within int
+static int policy_grad_rows_check(const std::string& who, int32_t n) {
+  if (n <= 0) return fail(who + ": n must be positive");
+  if (n > (1 << 27)) return fail(who + ": n must be at most 2^27");
+  return 0;
+}
+
+static int policy_grad_workspace(const char* fn, int shape_id, int32_t lidar_channels, int32_t n, size_t* out_bytes) {
+  if (policy_grad_rows_check(fn, n)) return 1;
+  const PolShape shape = pol_shape(shape_id, lidar_channels);
+  *out_bytes = policy_grad_layout(shape, n, nullptr, policy_layout(shape), nullptr, nullptr, nullptr, nullptr);
+  return 0;
+}
+
+static int policy_ppo_grad(const char* fn, const char* size_fn, int shape_id, const float* params, int32_t lidar_channels, int32_t n,
+                           const int64_t* index, const float* lidar, const float* inertial, const float* last_action, const float* action,
+                           const float* old_logp, const float* adv, const float* ret, const float* adv_mean_std, float clip_range,
+                           float vf_coef, float ent_coef, float* grad, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
+  const std::string who = std::string(fn);
+  if (policy_grad_rows_check(who, n)) return 1;
+  if (!params || !lidar || !inertial || !last_action || !action || !old_logp || !adv || !ret || !grad || !stats || !workspace)
+    return fail(who + ": null argument");
+  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if ((uintptr_t)grad & 15) return fail(who + ": grad must be 16-byte aligned");
+  if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
+  if ((uintptr_t)workspace & 255) return fail(who + ": workspace must be 256-byte aligned");
+  if ((uintptr_t)index & 7) return fail(who + ": index must be 8-byte aligned");
+  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)action, (const void*)old_logp, (const void*)adv,
+                        (const void*)ret, (const void*)adv_mean_std, (const void*)stats})
+    if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
+  GradTileArgs t; GradPlan g;
+  const PolShape shape = pol_shape(shape_id, lidar_channels);
+  const size_t need = policy_grad_layout(shape, n, static_cast<char*>(workspace), policy_layout(shape), grad, stats, &t, &g);
+  if (workspace_bytes < need)
+    return fail(who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + size_fn + " says " + std::to_string(need) + ")");
+  if (!std::isfinite(clip_range) || clip_range < 0.f) return fail(who + ": clip_range must be finite and >= 0");
+  t.action = action; t.old_logp = old_logp; t.adv = adv; t.ret = ret; t.adv_mean_std = adv_mean_std;
+  t.clip = clip_range; t.vf_coef = vf_coef; t.ent_coef = ent_coef; t.inv_n = 1.f / (float)n;
+  const PolicyIn in{lidar, inertial, last_action, index, n};
+  const hipStream_t s = (hipStream_t)stream;
+  // the tile grid covers the workspace's Bp rows (n rounded up to 32), not n: a 16-row shape's padding tile writes its rows too
+  const int Bp = g.L[POL_L_MU].R;
+  if (policy_launch(kPolicyGradKernels, shape_id, lidar_channels, params, Bp, stream, in, t)) return 1;
+  hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
+  TE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
+  TE_HIP(hipGetLastError());
   return 0;
 }
 
 __attribute__((visibility("default"))) int te_policy_grad_workspace_bytes(int32_t lidar_channels, int32_t n, size_t* out_bytes) {
+  size_t words;
   if (!out_bytes) return fail("te_policy_grad_workspace_bytes: null argument");
-  if (policy_grad_check(lidar_channels, n, "te_policy_grad_workspace_bytes")) return 1;
-  const PolShape shape = pol_shape(POL_SHAPE_DEFAULT, lidar_channels);
-  *out_bytes = policy_grad_layout(shape, n, nullptr, policy_layout(shape), nullptr, nullptr, nullptr, nullptr);
-  return 0;
+  if (policy_words(lidar_channels, &words)) return 1;
+  return policy_grad_workspace("te_policy_grad_workspace_bytes", POL_SHAPE_DEFAULT, lidar_channels, n, out_bytes);
+}
+
+__attribute__((visibility("default"))) int te_policy_grad_workspace_bytes_shaped(const te_policy_shape* shape, int32_t n, size_t* out_bytes) {
+  if (!out_bytes) return fail("te_policy_grad_workspace_bytes_shaped: null argument");
+  const int id = policy_shape_id(shape, "te_policy_grad_workspace_bytes_shaped");
+  if (id < 0) return 1;
+  return policy_grad_workspace("te_policy_grad_workspace_bytes_shaped", id, shape->lidar_channels, n, out_bytes);
 }
 
 __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* params, int32_t lidar_channels, int32_t n, const int64_t* index,
@@ -1831,34 +1879,24 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* param
                                                               const float* action, const float* old_logp, const float* adv, const float* ret,
                                                               const float* adv_mean_std, float clip_range, float vf_coef, float ent_coef,
                                                               float* grad, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
-  if (policy_grad_check(lidar_channels, n, "te_policy_ppo_grad")) return 1;
-  if (!params || !lidar || !inertial || !last_action || !action || !old_logp || !adv || !ret || !grad || !stats || !workspace)
-    return fail("te_policy_ppo_grad: null argument");
-  if ((uintptr_t)params & 15) return fail("te_policy_ppo_grad: params must be 16-byte aligned");
-  if ((uintptr_t)grad & 15) return fail("te_policy_ppo_grad: grad must be 16-byte aligned");
-  if ((uintptr_t)lidar & 7) return fail("te_policy_ppo_grad: lidar must be 8-byte aligned");
-  if ((uintptr_t)workspace & 255) return fail("te_policy_ppo_grad: workspace must be 256-byte aligned");
-  if ((uintptr_t)index & 7) return fail("te_policy_ppo_grad: index must be 8-byte aligned");
-  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)action, (const void*)old_logp, (const void*)adv,
-                        (const void*)ret, (const void*)adv_mean_std, (const void*)stats})
-    if ((uintptr_t)q & 3) return fail("te_policy_ppo_grad: float arrays must be 4-byte aligned");
-  GradTileArgs t; GradPlan g;
-  const PolShape shape = pol_shape(POL_SHAPE_DEFAULT, lidar_channels);
-  const size_t need = policy_grad_layout(shape, n, static_cast<char*>(workspace), policy_layout(shape), grad, stats, &t, &g);
-  if (workspace_bytes < need)
-    return fail("te_policy_ppo_grad: workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_policy_grad_workspace_bytes says " +
-                std::to_string(need) + ")");
-  if (!std::isfinite(clip_range) || clip_range < 0.f) return fail("te_policy_ppo_grad: clip_range must be finite and >= 0");
-  t.action = action; t.old_logp = old_logp; t.adv = adv; t.ret = ret; t.adv_mean_std = adv_mean_std;
-  t.clip = clip_range; t.vf_coef = vf_coef; t.ent_coef = ent_coef; t.inv_n = 1.f / (float)n;
-  const PolicyIn in{lidar, inertial, last_action, index, n};
-  const hipStream_t s = (hipStream_t)stream;
-  if (policy_launch(kPolicyGradKernels, POL_SHAPE_DEFAULT, lidar_channels, params, n, stream, in, t)) return 1;
-  hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
-  TE_HIP(hipGetLastError());
-  hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
-  TE_HIP(hipGetLastError());
-  return 0;
+  size_t words;
+  if (policy_words(lidar_channels, &words)) return 1;
+  return policy_ppo_grad("te_policy_ppo_grad", "te_policy_grad_workspace_bytes", POL_SHAPE_DEFAULT, params, lidar_channels, n, index, lidar,
+                         inertial, last_action, action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef, grad, stats, workspace,
+                         workspace_bytes, stream);
+}
+
+__attribute__((visibility("default"))) int te_policy_ppo_grad_shaped(const float* params, const te_policy_shape* shape, int32_t n,
+                                                                     const int64_t* index, const float* lidar, const float* inertial,
+                                                                     const float* last_action, const float* action, const float* old_logp,
+                                                                     const float* adv, const float* ret, const float* adv_mean_std,
+                                                                     float clip_range, float vf_coef, float ent_coef, float* grad, float* stats,
+                                                                     void* workspace, size_t workspace_bytes, void* stream) {
+  const int id = policy_shape_id(shape, "te_policy_ppo_grad_shaped");
+  if (id < 0) return 1;
+  return policy_ppo_grad("te_policy_ppo_grad_shaped", "te_policy_grad_workspace_bytes_shaped", id, params, shape->lidar_channels, n, index,
+                         lidar, inertial, last_action, action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef, grad, stats,
+                         workspace, workspace_bytes, stream);
 }
 
 // ---- optimiser step (te_policy_opt.hpp): every check is on the host, before any launch

@@ -223,7 +223,8 @@ def require_f32(who: str, name: str, t: torch.Tensor, shape, device: torch.devic
 
 
 GRAD_DEFAULT_ONLY = ("the gradient kernel te_policy_ppo_grad serves the default shape only (features_dim 256, net_arch (64, 64)): "
-                     "PPOConfig.fused_update and fused_optimizer are not available for this policy; without them update() runs autograd")
+                     "PPOConfig.fused_update and fused_optimizer are not available for this policy; without them update() runs autograd.  "
+                     "PPOConfig.fused_update_wide (with fused_update) asks for te_policy_ppo_grad_shaped, which serves every shape FusedPolicy does")
 
 
 class FusedPolicy:
@@ -242,7 +243,6 @@ class FusedPolicy:
         if self.device.type != "cuda":
             raise ValueError("FusedPolicy runs the HIP kernel te_policy_act: the policy must live on a GPU")
         self.shape = check_policy_shape(self.lidar_channels, self.features_dim, self.net_arch)    # the te_policy_shape of every call
-        self.default_shape = is_default_shape(self.features_dim, self.net_arch)
         words = policy_param_words(self.lidar_channels, self.features_dim, self.net_arch)
         if sum(p.numel() for p in params) != words:
             raise ValueError(f"policy has {sum(p.numel() for p in params)} parameters, te_policy_act's layout {words}: not a LidarInertialActionPolicy")
@@ -290,11 +290,11 @@ class FusedPolicy:
         """The gradient of PPO's loss over the minibatch rows `index` (int64 [B]; None: every row) of the rollout tensors obs,
         action [M, 4], old_logp, adv and ret [M], in the packed layout, into grad_out [te_policy_param_words] (16-byte aligned);
         stats_out [4] = pg, vl, ent, clip_frac.  adv_mean_std [2] (mean, unbiased std of adv over the minibatch) normalises the
-        advantage; None uses it as it is.  One te_policy_ppo_grad call: three launches, no host synchronisation.  The
-        workspace (~17.5 KB per row) is owned here and grows on demand, which a capturing stream does not allow: make the first
-        call of a size outside capture."""
-        if not self.default_shape:
-            raise ValueError(GRAD_DEFAULT_ONLY)
+        advantage; None uses it as it is.  One te_policy_ppo_grad_shaped call, for every shape FusedPolicy serves: three launches,
+        no host synchronisation; for the default shape bitwise te_policy_ppo_grad.  The workspace (per row 17 280 B for the default
+        shape, 31 616 B for features_dim 512 with net_arch (128, 256, 512) or (512, 128, 256), at 3 LIDAR channels; plus the split-K
+        partials: 17.8 KB and 33.2 / 33.7 KB per row in all at 65 536 rows) is owned here and grows on demand, which a capturing stream does not allow:
+        make the first call of a size outside capture."""
         lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
         m = lidar.shape[0]
         b = m if index is None else index.shape[0]
@@ -313,7 +313,7 @@ class FusedPolicy:
             raise ValueError("FusedPolicy.ppo_grad: the minibatch is empty")
         lib = _lib.load()
         need = C.c_size_t()
-        _lib.check(lib.te_policy_grad_workspace_bytes(self.lidar_channels, b, C.byref(need)), "te_policy_grad_workspace_bytes")
+        _lib.check(lib.te_policy_grad_workspace_bytes_shaped(C.byref(self.shape), b, C.byref(need)), "te_policy_grad_workspace_bytes_shaped")
         ws = getattr(self, "_grad_ws", None)
         if ws is None or ws.numel() < need.value:
             if torch.cuda.is_current_stream_capturing():
@@ -323,10 +323,11 @@ class FusedPolicy:
             ws = self._grad_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            _lib.check(lib.te_policy_ppo_grad(self.params.data_ptr(), self.lidar_channels, b, _ptr(index), lidar.data_ptr(), inertial.data_ptr(),
-                                              last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(),
-                                              _ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef), grad_out.data_ptr(),
-                                              stats_out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "te_policy_ppo_grad")
+            _lib.check(lib.te_policy_ppo_grad_shaped(self.params.data_ptr(), C.byref(self.shape), b, _ptr(index), lidar.data_ptr(),
+                                                     inertial.data_ptr(), last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(),
+                                                     adv.data_ptr(), ret.data_ptr(), _ptr(adv_mean_std), float(clip), float(vf_coef),
+                                                     float(ent_coef), grad_out.data_ptr(), stats_out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                     stream), "te_policy_ppo_grad_shaped")
 
     def _call(self, obs, eps, outs):
         lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
@@ -517,13 +518,23 @@ class PPOConfig:
     fused_advantages: bool = False
     # the shape of the policy PPO builds when it is given none: the trunk's width and the widths of the pi / vf heads' hidden layers
     # (LidarInertialActionPolicy).  The reference's trained networks are features_dim=512 with net_arch=(128, 256, 512) or (512, 128, 256).
-    # fused_update and fused_optimizer serve the default shape only
+    # fused_update and fused_optimizer serve the default shape, and the other two only with fused_update_wide
     features_dim: int = 256
     net_arch: tuple = (64, 64)
+    # fused_update (and with it fused_optimizer) for a policy of the other served shapes: features_dim 512 with net_arch (128, 256, 512) or
+    # (512, 128, 256), through te_policy_ppo_grad_shaped.  Needs fused_update; changes nothing for the default shape.  A switch of its own
+    # because for these shapes the fused forward is slower than PyTorch's (fused_forward above), and the fused gradient pays at small
+    # minibatches only.  Measured, one minibatch (gradient + clip + Adam) against autograd fp32 (DESIGN.md 7,
+    # profiles/policy_grad_shapes.json): at 8 192 rows 1.65 against 3.47 ms for (128, 256, 512) and 1.93 against 4.07 ms for
+    # (512, 128, 256), 2.1 x faster; at 65 536 rows 9.94 against 10.41 ms (1.05 x) and 11.78 against 10.25 ms: 0.87 x, SLOWER than autograd.
+    # Off by default
+    fused_update_wide: bool = False
 
     def __post_init__(self):
         if self.fused_optimizer and not self.fused_update:
             raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
+        if self.fused_update_wide and not self.fused_update:
+            raise ValueError("PPOConfig.fused_update_wide widens fused_update to every served shape: it needs fused_update")
 
 
 class RolloutBuffer:
@@ -614,8 +625,12 @@ class PPO:
         torch.manual_seed(seed)
         self.policy = (policy or LidarInertialActionPolicy(lidar_shape=tuple(env.lidar.shape[1:]), features_dim=self.cfg.features_dim,
                                                            net_arch=self.cfg.net_arch)).to(self.device)
+        if self.cfg.fused_update_wide and not self.cfg.fused_update:    # set after PPOConfig's own check
+            raise ValueError("PPOConfig.fused_update_wide widens fused_update to every served shape: it needs fused_update")
         if (self.cfg.fused_update or self.cfg.fused_optimizer) and not is_default_shape(*policy_shape(self.policy)[1:]):
-            raise ValueError(GRAD_DEFAULT_ONLY)
+            if not self.cfg.fused_update_wide:
+                raise ValueError(GRAD_DEFAULT_ONLY)
+            check_policy_shape(*policy_shape(self.policy))      # an unserved shape: the ValueError that lists the served ones
         fused = bool(self.cfg.fast_learner) and self.device.type == "cuda"
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=self.cfg.learning_rate, eps=1e-5, **({"fused": True} if fused else {}))
         shapes = {"lidar": tuple(env.lidar.shape[1:]), "inertial_data": (env.inertial.shape[1],), "last_action": (4,)}

@@ -516,6 +516,23 @@ int te_policy_ppo_grad(const float* params, int32_t lidar_channels, int32_t n, c
                        const float* ret, const float* adv_mean_std, float clip_range, float vf_coef, float ent_coef, float* grad,
                        float* stats, void* workspace, size_t workspace_bytes, void* stream);
 
+/* te_policy_ppo_grad for a packed buffer of any served te_policy_shape: the same loss, arguments, checks (null, alignment, workspace
+ * size, clip_range, n <= 2^27; an unserved shape fails as in te_policy_shape_check, before any launch), outputs and guarantees
+ * (fixed sum orders, bitwise repeatable, three launches, capturable); grad has te_policy_param_words_shaped(shape) words.  With the
+ * default shape both calls are the unshaped ones: the same size, and bitwise the same grad and stats.
+ * workspace: at least te_policy_grad_workspace_bytes_shaped(shape, n) bytes.  Per row it holds every layer's input and
+ * pre-activation gradient: 4 320 floats = 17 280 B for the default shape, 7 904 floats = 31 616 B for either features_dim 512 shape
+ * (lidar_channels 3; 192 floats fewer for 2), for n rounded up to 32 rows whatever the shape, each array rounded up to 256 B; then
+ * the split-K partials, one copy of the gradient and the statistics per 2 048 rows of a layer's reduction (conv1 has 12 n rows, conv2
+ * 3 n).  At lidar_channels 3 the function returns 4 099 328 / 5 142 784 B for n <= 32 and 2 175 067 904 / 2 208 458 496 B
+ * (33 189 / 33 698 B per row) for n = 65 536 with hidden 128, 256, 512 / 512, 128, 256; 1 166 870 272 B (17 805 B per row) there for
+ * the default shape. */
+int te_policy_grad_workspace_bytes_shaped(const te_policy_shape* shape, int32_t n, size_t* out_bytes);
+int te_policy_ppo_grad_shaped(const float* params, const te_policy_shape* shape, int32_t n, const int64_t* index, const float* lidar,
+                              const float* inertial, const float* last_action, const float* action, const float* old_logp,
+                              const float* adv, const float* ret, const float* adv_mean_std, float clip_range, float vf_coef,
+                              float ent_coef, float* grad, float* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The optimiser step of the PPO learner: clip_grad_norm_ followed by torch.optim.Adam (the non-fused form; no weight decay, no
  * amsgrad: SB3's optimiser) over ONE flat buffer of `words` fp32 parameters, e.g. the packed buffer of te_policy_act with the
  * gradient of te_policy_ppo_grad.  The call knows nothing of the policy's layers: any words in [1, 2^40] is served.

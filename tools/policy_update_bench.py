@@ -5,6 +5,9 @@ te_policy_opt.hpp) at 2 048 (PPOConfig.batch_size's default), 8 192, 16 384 and 
 minibatch (gradient + clip + Adam) on a collected stage03 rollout; the te_policy_ppo_grad call alone against its fp32 MFMA bound;
 then tools/ppo_split.py's 65 536-env collect + update with fused_forward=True, fused_update=True.  One JSON document on stdout.
     python tools/policy_update_bench.py [n_envs_for_split] [n_steps] [epochs]
+    python tools/policy_update_bench.py --shapes [--rows 8192,65536] [--repeats 5] [--features-dim 512 --net-arch 128,256,512]
+--shapes: the same minibatch for the wide shapes the gradient kernel serves (both, or the one given): autograd fp32 against
+fused_update + fused_update_wide, and te_policy_ppo_grad_shaped alone, the three forms alternating, median [min, max] over the repeats.
 Bound: forward + activation gradients (all but conv1's, inertial.0's and action.0's inputs) + weight gradients, 2 FLOP per MAC, at
 the 157.3 TF fp32 MFMA peak."""
 import json
@@ -18,9 +21,10 @@ from dronechase_amd import default_config
 from dronechase_amd.batched_env import BatchedEnv
 from dronechase_amd.ppo import PPO, PPOConfig
 
-N_SPLIT = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-T = int(sys.argv[2]) if len(sys.argv) > 2 else 32
-E = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+_pos = [] if "--shapes" in sys.argv else sys.argv[1:]
+N_SPLIT = int(_pos[0]) if len(_pos) > 0 else 65536
+T = int(_pos[1]) if len(_pos) > 1 else 32
+E = int(_pos[2]) if len(_pos) > 2 else 2
 FWD = 32 * 48 * 12 + 64 * 128 * 3 + (15 * 128 + 2 * 128 * 128) + (4 * 128 + 2 * 128 * 128) + 448 * 256 + 2 * (256 * 64 + 64 * 64) + 64 * 5
 MACS_PER_ROW = 3 * FWD - (32 * 48 * 12 + 15 * 128 + 4 * 128)
 PEAK_TFLOPS = 157.3
@@ -33,6 +37,63 @@ def timed(fn, reps):
     torch.cuda.synchronize()
     return (time.perf_counter() - t) / reps
 
+
+def shapes_mode(argv):
+    """One minibatch per form and repeat, the forms alternating; ms, median [min, max]."""
+    import statistics
+    opt = lambda name, default: argv[argv.index(name) + 1] if name in argv else default
+    rows_list = [int(r) for r in opt("--rows", "8192,65536").split(",")]
+    repeats = int(opt("--repeats", "5"))
+    shapes = {"reference BO": (512, (128, 256, 512)), "reference learn": (512, (512, 128, 256))}
+    if "--features-dim" in argv or "--net-arch" in argv:
+        shapes = {"given": (int(opt("--features-dim", "256")), tuple(int(w) for w in opt("--net-arch", "64,64").split(",")))}
+    res = {"repeats": repeats, "unit": "ms per minibatch (gradient + clip + Adam), median [min, max]", "shapes": []}
+    for name, (f, arch) in shapes.items():
+        widths = (f,) + arch
+        fwd = 32 * 48 * 12 + 64 * 128 * 3 + (15 * 128 + 2 * 128 * 128) + (4 * 128 + 2 * 128 * 128) + 448 * f + \
+            2 * sum(a * b for a, b in zip(widths, widths[1:])) + arch[-1] * 5
+        macs = 3 * fwd - (32 * 48 * 12 + 15 * 128 + 4 * 128)
+        for rows in rows_list:
+            forms, envs = {}, []
+            for key, kw in (("autograd_fp32", {}), ("fused_update_wide", {"fused_update": True, "fused_update_wide": True})):
+                env = BatchedEnv(default_config("stage03", n_envs=rows), "cuda:0")
+                ppo = PPO(env, PPOConfig(n_steps=1, batch_size=rows, n_epochs=1, use_graph=False, features_dim=f, net_arch=arch, **kw), seed=3)
+                ppo.collect()
+                for _ in range(3):
+                    ppo.update()
+                forms[key] = ppo.update
+                envs.append((env, ppo))
+            ppo = envs[1][1]
+            b = ppo.buf
+            obs = {k: v.reshape(rows, *v.shape[2:]) for k, v in b.obs.items()}
+            idx = torch.randperm(rows, device="cuda:0")
+            ms = torch.tensor([0.0, 1.0], device="cuda:0")
+            st = torch.empty(4, device="cuda:0")
+            grad = torch.empty_like(ppo._flat_grad)
+            forms["te_policy_ppo_grad_shaped"] = lambda: ppo.fused_grad.ppo_grad(obs, idx, b.actions.reshape(rows, 4), b.logp.reshape(-1),
+                                                                                 b.adv.reshape(-1), b.ret.reshape(-1), ms, 0.2, 0.5, 0.0, grad, st)
+            forms["te_policy_ppo_grad_shaped"]()
+            times = {k: [] for k in forms}
+            for _ in range(repeats):
+                for k, fn in forms.items():
+                    times[k].append(timed(fn, 10) * 1e3)
+            rec = {"shape": name, "features_dim": f, "net_arch": list(arch), "rows": rows, "macs_per_row": macs,
+                   "bound_ms": 2.0 * macs * rows / (PEAK_TFLOPS * 1e12) * 1e3}
+            for k, ts in times.items():
+                rec[k] = {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+            rec["autograd_over_fused"] = rec["autograd_fp32"]["median"] / rec["fused_update_wide"]["median"]
+            rec["te_policy_ppo_grad_shaped_TFLOPS"] = 2.0 * macs * rows / (rec["te_policy_ppo_grad_shaped"]["median"] * 1e-3) / 1e12
+            res["shapes"].append(rec)
+            for env, _ in envs:
+                env.close()
+            del envs, forms, ppo, b, obs, grad
+            torch.cuda.empty_cache()
+    print(json.dumps(res, indent=1))
+
+
+if "--shapes" in sys.argv:
+    shapes_mode(sys.argv)
+    sys.exit(0)
 
 out = {"macs_per_row": MACS_PER_ROW, "minibatch": []}
 for rows in (2048, 8192, 16384, 65536):
