@@ -45,6 +45,7 @@
 #include "te_engage.hpp"
 #include "te_engage_slots.hpp"
 #include "te_policy.hpp"
+#include "te_policy_bf16.hpp"
 #include "te_wingman.hpp"
 #include "te_policy_grad.hpp"
 #include "te_policy_opt.hpp"
@@ -1092,6 +1093,37 @@ static const PolKernel<PolicyIO> kPolicyActKernels[POL_SHAPE_COUNT][2] = TE_POL_
 static const PolKernel<PolicyIn, Params, int, float*> kPolicyDriveKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_drive_kernel);
 static const PolKernel<PolicyIn, GradTileArgs> kPolicyGradKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_grad_tile_kernel);
 
+// te_policy_act_bf16's instances (te_policy_bf16.hpp) and their launch: policy_launch with the bf16 LDS plan and the second weight buffer
+using PolBf16Kernel = void (*)(PolicyParams, PolicyBf16, PolicyIO);
+static const PolBf16Kernel kPolicyActBf16Kernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_act_bf16_kernel);
+
+static int policy_launch_bf16(int shape_id, int32_t lidar_channels, const float* params, const uint16_t* weights, int n, void* stream,
+                              const PolicyIO& io) {
+  static std::map<const void*, uint64_t> opted;
+  static std::mutex opted_lock;
+  const PolShape shape = pol_shape(shape_id, lidar_channels);
+  const PolLdsB lds = pol_lds_plan_bf16(shape);
+  const PolBf16Kernel fn = kPolicyActBf16Kernels[shape_id][lidar_channels - 2];
+  int dev = 0;
+  TE_HIP(hipGetDevice(&dev));
+  {
+    std::lock_guard<std::mutex> hold(opted_lock);
+    uint64_t& bits = opted[reinterpret_cast<const void*>(fn)];
+    if (dev < 64 && !(bits >> dev & 1)) {
+      TE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes));
+      bits |= 1ull << dev;
+    }
+  }
+  PolicyParams P = policy_layout(shape);
+  P.base = params;
+  PolicyBf16 W = policy_bf16_layout(shape);
+  W.base = weights;
+  const dim3 grid((unsigned)((n + lds.M - 1) / lds.M));
+  hipLaunchKernelGGL(fn, grid, dim3(lds.threads), (size_t)lds.bytes, (hipStream_t)stream, P, W, io);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
 static std::string shape_text(const PolShape& s) {
   std::string t = "features_dim " + std::to_string(s.F) + ", hidden";
   for (int i = 0; i < s.n_hidden; ++i) t += (i ? ", " : " ") + std::to_string(s.h[i]);
@@ -1774,6 +1806,47 @@ __attribute__((visibility("default"))) int te_policy_act_shaped(const float* par
   if (id < 0) return 1;
   return policy_act("te_policy_act_shaped", id, params, shape->lidar_channels, n, lidar, inertial, last_action, eps, mu, value, action, logp,
                     action_env, stream);
+}
+
+__attribute__((visibility("default"))) int te_policy_bf16_words(const te_policy_shape* shape, size_t* out_halfwords) {
+  if (!out_halfwords) return fail("te_policy_bf16_words: null argument");
+  const int id = policy_shape_id(shape, "te_policy_bf16_words");
+  if (id < 0) return 1;
+  *out_halfwords = (size_t)policy_bf16_layout(pol_shape(id, shape->lidar_channels)).words;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_pack_bf16(const float* params, const te_policy_shape* shape, uint16_t* out, void* stream) {
+  const int id = policy_shape_id(shape, "te_policy_pack_bf16");
+  if (id < 0) return 1;
+  if (!params || !out) return fail("te_policy_pack_bf16: null argument");
+  if ((uintptr_t)params & 15) return fail("te_policy_pack_bf16: params must be 16-byte aligned");
+  if ((uintptr_t)out & 15) return fail("te_policy_pack_bf16: out must be 16-byte aligned");
+  const PolPackPlan plan = policy_pack_plan(pol_shape(id, shape->lidar_channels));
+  hipLaunchKernelGGL(policy_pack_bf16_kernel, dim3((unsigned)((plan.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, plan,
+                     reinterpret_cast<__bf16*>(out));
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_act_bf16(const float* params, const uint16_t* weights_bf16, const te_policy_shape* shape,
+                                                              int32_t n, const float* lidar, const float* inertial, const float* last_action,
+                                                              const float* eps, float* mu, float* value, float* action, float* logp,
+                                                              float* action_env, void* stream) {
+  const std::string who = "te_policy_act_bf16";
+  const int id = policy_shape_id(shape, "te_policy_act_bf16");
+  if (id < 0) return 1;
+  if (n <= 0) return fail(who + ": n must be positive");
+  if (!params || !weights_bf16 || !lidar || !inertial || !last_action || !mu || !value) return fail(who + ": null argument");
+  if (eps && (!action || !logp || !action_env)) return fail(who + ": eps given, so action, logp and action_env must be too");
+  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if ((uintptr_t)weights_bf16 & 15) return fail(who + ": weights_bf16 must be 16-byte aligned");
+  if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
+  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)eps, (const void*)mu, (const void*)value,
+                        (const void*)action, (const void*)logp, (const void*)action_env})
+    if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
+  const PolicyIO io{lidar, inertial, last_action, eps, mu, value, eps ? action : nullptr, eps ? logp : nullptr, eps ? action_env : nullptr, n};
+  return policy_launch_bf16(id, shape->lidar_channels, params, weights_bf16, n, stream, io);
 }
 
 // te_drive_wingman and te_drive_wingman_shaped behind their shape checks

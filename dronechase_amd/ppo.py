@@ -233,9 +233,16 @@ class FusedPolicy:
     512 with (128, 256, 512) or (512, 128, 256)); any other shape is a ValueError that lists them.  The weights are packed into ONE device buffer that keeps its address for the life of
     this object; refresh() repacks the module's current weights into it in place, so a HIP graph that captured a call sees them.
     Call refresh() after every change of the module's weights (PPO does, at the start of every collect()).
-    After bind_parameters() the module's parameters are views of the packed buffer and there is nothing left to repack."""
+    After bind_parameters() the module's parameters are views of the packed buffer and there is nothing left to repack.
+    precision="bf16": forward and act go to te_policy_act_bf16 (bf16 operands on the bf16 MFMA, fp32 accumulation; the numerics
+    contract is in include/threatengage.h).  The object then owns a second buffer, the weights rounded to bf16 (te_policy_pack_bf16),
+    at a stable address too; refresh() repacks it with one more launch, also after bind_parameters().  ppo_grad is untouched: it
+    reads the fp32 buffer."""
 
-    def __init__(self, policy: nn.Module):
+    def __init__(self, policy: nn.Module, precision: str = "fp32"):
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"FusedPolicy: precision must be 'fp32' or 'bf16', not {precision!r}")
+        self.precision = precision
         self.policy = policy
         self.lidar_channels, self.features_dim, self.net_arch = policy_shape(policy)
         params = _packed_order(policy)
@@ -247,12 +254,22 @@ class FusedPolicy:
         if sum(p.numel() for p in params) != words:
             raise ValueError(f"policy has {sum(p.numel() for p in params)} parameters, te_policy_act's layout {words}: not a LidarInertialActionPolicy")
         self.params = torch.empty(words, dtype=torch.float32, device=self.device)
+        self.weights_bf16 = None
+        if precision == "bf16":
+            half = C.c_size_t()
+            _lib.check(_lib.load().te_policy_bf16_words(C.byref(self.shape), C.byref(half)), "te_policy_bf16_words")
+            self.weights_bf16 = torch.empty(int(half.value), dtype=torch.int16, device=self.device)
         self.bound = False
         self.refresh()
 
     def refresh(self) -> None:
         if not self.bound:      # bound: the parameters ARE the buffer (and torch.cat(out=) onto its own inputs raises)
             pack_policy(self.policy, out=self.params)
+        if self.weights_bf16 is not None:       # the fp32 buffer is the master copy: round it again, in place, on the current stream
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                _lib.check(_lib.load().te_policy_pack_bf16(self.params.data_ptr(), C.byref(self.shape), self.weights_bf16.data_ptr(), stream),
+                           "te_policy_pack_bf16")
 
     @torch.no_grad()
     def bind_parameters(self) -> None:
@@ -338,6 +355,11 @@ class FusedPolicy:
                 require_f32("FusedPolicy", name, t, shape, self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if self.weights_bf16 is not None:
+                _lib.check(_lib.load().te_policy_act_bf16(self.params.data_ptr(), self.weights_bf16.data_ptr(), C.byref(self.shape), n,
+                                                          lidar.data_ptr(), inertial.data_ptr(), last_action.data_ptr(), _ptr(eps),
+                                                          *(_ptr(o) for o in outs), stream), "te_policy_act_bf16")
+                return
             _lib.check(_lib.load().te_policy_act_shaped(self.params.data_ptr(), C.byref(self.shape), n, lidar.data_ptr(), inertial.data_ptr(),
                                                         last_action.data_ptr(), _ptr(eps), *(_ptr(o) for o in outs), stream), "te_policy_act_shaped")
 
@@ -434,12 +456,14 @@ class PolicyDriver:
     the ally flown by a copy of the learning policy, apps/threatengage_runner/stage03/experiments/05/
     bo_exp05_vFinal_home_office_app.py:140,179) takes when the observations should not leave HBM.
     fused=True: the forward (and the sample) is one te_policy_act launch (FusedPolicy); the weights are repacked at every call,
-    so a policy trained in between is always the one that flies."""
+    so a policy trained in between is always the one that flies.  precision="bf16" (with fused=True): te_policy_act_bf16."""
     accepts_torch = True
 
-    def __init__(self, policy: nn.Module, fused: bool = False):
+    def __init__(self, policy: nn.Module, fused: bool = False, precision: str = "fp32"):
+        if precision != "fp32" and not fused:
+            raise ValueError("PolicyDriver: precision other than 'fp32' is the fused kernel's: it needs fused=True")
         self.policy = policy
-        self.fused = FusedPolicy(policy) if fused else None
+        self.fused = FusedPolicy(policy, precision=precision) if fused else None
         self.low = None
 
     @torch.no_grad()
@@ -481,8 +505,20 @@ class PPOConfig:
     # Off by default: the outputs agree with the module's to ~1.5e-7 (measured), not bit for bit (another summation order)
     # It serves the shapes FusedPolicy lists, and pays for the default shape only: at 65 536 rows the launch takes 0.56 ms against PyTorch's
     # 1.14 ms for the default, but 3.06 against 1.84 ms for features_dim 512 with net_arch (128, 256, 512) and 3.83 against 2.04 ms with
-    # (512, 128, 256) (measured, DESIGN.md 7, profiles/policy_shapes.json): for those, leave it off unless the single launch matters more
+    # (512, 128, 256) (measured, DESIGN.md 7, profiles/policy_shapes.json): for those, leave it off unless the single launch matters more, or add fused_forward_bf16
     fused_forward: bool = False
+    # fused_forward through te_policy_act_bf16: weights and every layer's input rounded to bf16, the GEMMs on the bf16 MFMA with fp32
+    # accumulation (FusedPolicy(precision="bf16"); the contract is in include/threatengage.h).  Needs fused_forward; applies to collect()
+    # and to the bootstrap value, in both collect paths; update() is untouched.  What it costs: old_logp and the stored values come from
+    # the bf16 mean and value while update()'s forward is fp32, so the first epoch's ratio is not exactly 1.
+    # Measured on the MI355X (profiles/policy_bf16.json): at 65 536 rows the launch takes 0.246 ms for the default shape, 0.548 ms
+    # for features_dim 512 with net_arch (128, 256, 512) and 0.549 ms with (512, 128, 256), against PyTorch's fp32 forward at 1.158 / 1.849 /
+    # 2.049 ms, PyTorch under autocast(bfloat16) at 0.886 / 1.064 / 1.070 ms and the fp32 launch at 0.563 / 3.069 / 3.817 ms; collect() of
+    # (128, 256, 512) at 65 536 envs runs 1.02 ms per step against 2.38 (PyTorch) and 3.70 (fp32 launch).  The gap: mu and value differ from the
+    # fp32 module's by at most 3.3e-4 on the test inputs (outputs of magnitude 0.02 to 0.2), and over 131 072 rows of that collect()
+    # |log ratio| of the first epoch before any step was 1.1e-4 on average and 9.8e-4 at most, against clip_range 0.2.
+    # Off by default
+    fused_forward_bf16: bool = False
     # update(): the minibatch's loss gradient in ONE ABI call (te_policy_ppo_grad, FusedPolicy.ppo_grad: forward, loss, backward and
     # deterministic split-K weight gradients in HIP, the rows read through the minibatch index) instead of the PyTorch forward +
     # autograd; gradient clipping, the all-reduce and Adam stay as they are (with fast_learner: fused Adam, no autocast).
@@ -535,6 +571,8 @@ class PPOConfig:
             raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
         if self.fused_update_wide and not self.fused_update:
             raise ValueError("PPOConfig.fused_update_wide widens fused_update to every served shape: it needs fused_update")
+        if self.fused_forward_bf16 and not self.fused_forward:
+            raise ValueError("PPOConfig.fused_forward_bf16 is fused_forward's launch with bf16 operands: it needs fused_forward")
 
 
 class RolloutBuffer:
@@ -677,7 +715,9 @@ class PPO:
             raise ValueError("PPOConfig.fused_advantages runs the HIP kernels of te_rollout_gae and te_adv_stats: it needs a GPU device")
         if self.cfg.fused_optimizer and not self.cfg.fused_update:      # set after PPOConfig's own check
             raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
-        self.fused = FusedPolicy(self.policy) if self.cfg.fused_forward else None
+        if self.cfg.fused_forward_bf16 and not self.cfg.fused_forward:      # set after PPOConfig's own check
+            raise ValueError("PPOConfig.fused_forward_bf16 is fused_forward's launch with bf16 operands: it needs fused_forward")
+        self.fused = FusedPolicy(self.policy, precision="bf16" if self.cfg.fused_forward_bf16 else "fp32") if self.cfg.fused_forward else None
         self.fused_grad = (self.fused or FusedPolicy(self.policy)) if self.cfg.fused_update else None
         if self.cfg.fused_optimizer:    # the packed buffer becomes the single copy of the weights; the torch optimiser is dropped
             self.fused_grad.bind_parameters()

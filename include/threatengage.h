@@ -493,6 +493,34 @@ int te_policy_act_shaped(const float* params, const te_policy_shape* shape, int3
                          const float* last_action, const float* eps, float* mu, float* value, float* action, float* logp,
                          float* action_env, void* stream);
 
+/* te_policy_act_shaped with bf16 operands on the bf16 MFMA (v_mfma_f32_16x16x32_bf16), opt-in, for every served shape and
+ * lidar_channels 2 and 3 (dronechase_amd/csrc/te_policy_bf16.hpp).  Numerics contract:
+ *   - weights are rounded once to bf16, round-to-nearest-even, by te_policy_pack_bf16; the fp32 packed buffer stays the master copy;
+ *   - the input of every weight layer is rounded to bf16 (round-to-nearest-even) where it is stored for the MFMA: the LIDAR patch,
+ *     inertial_data, last_action, every hidden activation, the concat, the trunk, the head tiles and each head's last hidden tile;
+ *   - products are accumulated in fp32 by the MFMA, the accumulator starting from the fp32 bias; ReLU and tanhf run in fp32 on the
+ *     accumulator and the result is rounded when it is stored;
+ *   - mu and value are fp32 fmaf sums, one thread per row, of the fp32 weights and bias over the bf16 last hidden tile;
+ *   - log_std, the sample, logp and the clamp are te_policy_act's, in fp32;
+ *   - a row's outputs do not depend on n or on the other rows, and repeated calls are bitwise equal.
+ * The outputs therefore differ from te_policy_act_shaped's by bf16 rounding (measured: README).
+ *
+ * weights_bf16 is ONE device buffer of te_policy_bf16_words(shape) uint16 elements, 16-byte aligned: for every weight layer below mu
+ * and value, in the order of the fp32 buffer (lidar.0, lidar.2, inertial.{0,2,4}, action.{0,2,4}, final.0, pi.{0,2,..},
+ * vf.{0,2,..}), the weight [N][Kp] row-major as bf16 bit patterns, Kp = K rounded up to a multiple of 32, columns K .. Kp - 1 zero
+ * (every row starts on a 64-byte boundary of the buffer).  Biases, mu, value and log_std are not in it: the call reads them from
+ * `params`.  te_policy_pack_bf16 fills it from `params` (the fp32 packed buffer of the same shape) in one launch on `stream`, no host
+ * synchronisation; call it again after every change of `params`.
+ *
+ * te_policy_act_bf16: the arguments, optional pointers, alignment rules and checks of te_policy_act_shaped, plus weights_bf16.  Every
+ * argument error returns non-zero before any launch with te_last_error set; an unserved shape is refused with the served list.
+ * Enqueues on `stream` only: a HIP graph can capture it. */
+int te_policy_bf16_words(const te_policy_shape* shape, size_t* out_halfwords);
+int te_policy_pack_bf16(const float* params, const te_policy_shape* shape, uint16_t* out, void* stream);
+int te_policy_act_bf16(const float* params, const uint16_t* weights_bf16, const te_policy_shape* shape, int32_t n, const float* lidar,
+                       const float* inertial, const float* last_action, const float* eps, float* mu, float* value, float* action,
+                       float* logp, float* action_env, void* stream);
+
 /* The gradient of PPO's loss (dronechase_amd/ppo.py PPO.update) for one minibatch of n rows, in fp32:
  *   mu, v  = the policy of te_policy_act on row i;  sigma = exp(log_std)
  *   logp   = sum_j (-(action_j - mu_j)^2 / (2 sigma_j^2) - log_std_j - log(2 pi) / 2)

@@ -5,6 +5,10 @@
 --features-dim / --net-arch: the shape of the policy of those two parts (default 256 and 64,64).
 Then every served shape at 65 536 rows: the fused launch (forward only, FusedPolicy.forward) against the op-by-op PyTorch forward of
 the same module, five alternating repeats each (median, min and max), written to profiles/policy_shapes.json as well.
+Then te_policy_act_bf16 (FusedPolicy(precision="bf16")) for every served shape at 8 192 and 65 536 rows against the fp32 fused launch, the
+PyTorch fp32 forward and the PyTorch forward under torch.autocast(bfloat16), five alternating repeats each (median, min, max), and the PPO
+collect split of net_arch (128, 256, 512) with PPOConfig.fused_forward_bf16 off and on, written to profiles/policy_bf16.json; --only-bf16 runs
+this part alone.  TE_POLICY_BF16_RECORD=<path>: the JSON lines tests/test_policy_bf16.py wrote there become the file's "numerics".
 Bound, default shape: 267 k MACs per row -> 65 536 rows = 35.0 GFLOP = 0.22 ms at the 157.3 TF fp32 MFMA peak."""
 import argparse
 import json
@@ -26,6 +30,7 @@ ap.add_argument("n_steps", nargs="?", type=int, default=32)
 ap.add_argument("--features-dim", type=int, default=256)
 ap.add_argument("--net-arch", type=lambda s: tuple(int(w) for w in s.split(",")), default=(64, 64))
 ap.add_argument("--no-collect", action="store_true", help="skip the PPO collect split")
+ap.add_argument("--only-bf16", action="store_true", help="only the bf16 part (profiles/policy_bf16.json)")
 args = ap.parse_args()
 N_COLLECT, T = args.n_collect, args.n_steps
 SERVED = {"default": (256, (64, 64)), "reference BO": (512, (128, 256, 512)), "reference learn": (512, (512, 128, 256))}
@@ -48,6 +53,96 @@ def timed(fn, reps):
     torch.cuda.synchronize()
     return (time.perf_counter() - t) / reps
 
+
+def bf16_part():
+    """te_policy_act_bf16 against the three forwards it competes with, and the collect split; profiles/policy_bf16.json."""
+    REPEATS = 5
+    stat = lambda xs: {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
+    doc = {"repeats": REPEATS, "rows": [8192, 65536], "forward_ms": [], "collect": None, "numerics": []}
+    for rows in doc["rows"]:
+        obs = {"lidar": torch.rand(rows, 3, 13, 26, device="cuda:0"), "inertial_data": torch.rand(rows, 15, device="cuda:0") * 2 - 1,
+               "last_action": torch.rand(rows, 4, device="cuda:0")}
+        for name, (fdim, arch) in SERVED.items():
+            torch.manual_seed(0)
+            policy = LidarInertialActionPolicy(features_dim=fdim, net_arch=arch).to("cuda:0")
+            f32, b16 = FusedPolicy(policy), FusedPolicy(policy, precision="bf16")
+
+            @torch.no_grad()
+            def torch_forward():
+                return policy(obs)
+
+            @torch.no_grad()
+            def torch_autocast():
+                with torch.autocast("cuda", dtype=torch.bfloat16):
+                    return policy(obs)
+
+            runs = {"fused_bf16": (lambda: b16.forward(obs), 100), "fused_fp32": (lambda: f32.forward(obs), 50),
+                    "pytorch_fp32": (torch_forward, 30), "pytorch_autocast_bf16": (torch_autocast, 30)}
+            for _ in range(5):
+                for fn, _reps in runs.values():
+                    fn()
+            t = {k: [] for k in runs}
+            for _ in range(REPEATS):
+                for k, (fn, reps) in runs.items():
+                    t[k].append(timed(fn, reps * (65536 // rows)) * 1e3)     # the same work per window at either size
+            med = {k: statistics.median(v) for k, v in t.items()}
+            flop = 2.0 * macs_per_row(fdim, arch) * rows
+            doc["forward_ms"].append({
+                "rows": rows, "name": name, "features_dim": fdim, "net_arch": list(arch), "bf16_halfwords": b16.weights_bf16.numel(),
+                **{k: stat(v) for k, v in t.items()},
+                "pytorch_fp32_over_fused_bf16": med["pytorch_fp32"] / med["fused_bf16"],
+                "pytorch_autocast_over_fused_bf16": med["pytorch_autocast_bf16"] / med["fused_bf16"],
+                "fused_fp32_over_fused_bf16": med["fused_fp32"] / med["fused_bf16"], "fused_bf16_TFLOPS": flop / med["fused_bf16"] / 1e9})
+            del f32, b16, policy
+        del obs
+        torch.cuda.empty_cache()
+
+    fdim, arch = SERVED["reference BO"]
+    env = BatchedEnv(default_config("stage03", n_envs=N_COLLECT), "cuda:0")
+    env.reset()
+    a = env.random_actions(1, 0)
+    for _ in range(20):
+        env.step(a, terminal=False)
+    t_env = timed(lambda: env.step(a, terminal=False), 200)
+    env.close()
+    col = {"n_envs": N_COLLECT, "n_steps": T, "features_dim": fdim, "net_arch": list(arch), "env_step_us": t_env * 1e6}
+    variants = {"pytorch_forward": {}, "fused_forward": {"fused_forward": True}, "fused_forward_bf16": {"fused_forward": True, "fused_forward_bf16": True}}
+    ppos, t_col = {}, {k: [] for k in variants}
+    for k, kw in variants.items():
+        env = BatchedEnv(default_config("stage03", n_envs=N_COLLECT), "cuda:0")
+        ppos[k] = PPO(env, PPOConfig(n_steps=T, batch_size=N_COLLECT, n_epochs=1, use_graph=True, features_dim=fdim, net_arch=arch, **kw), seed=3)
+        ppos[k].collect()                          # graph capture
+    for _ in range(REPEATS):
+        for k in variants:
+            t_col[k].append(timed(ppos[k].collect, 2))
+    for k in variants:
+        m = statistics.median(t_col[k])
+        col[k] = {"collect_us_per_step": stat([x / T * 1e6 for x in t_col[k]]), "collect_Msteps_per_s": T * N_COLLECT / m / 1e6,
+                  "policy_share_of_collect": 1.0 - t_env * T / m}
+    # what the switch costs PPO: old_logp is the bf16 forward's, update()'s forward is fp32, so log(ratio) of the first epoch is not 0
+    b = ppos["fused_forward_bf16"].buf
+    with torch.no_grad():
+        t0 = slice(0, 2)                            # two steps of the rollout: 131 072 rows at the default size
+        d, v = ppos["fused_forward_bf16"].policy.dist({k: o[t0].reshape(-1, *o.shape[2:]) for k, o in b.obs.items()})
+        lr = (d.log_prob(b.actions[t0].reshape(-1, 4)).sum(-1) - b.logp[t0].reshape(-1)).abs()
+        dv = (v - b.values[t0].reshape(-1)).abs()
+    col["first_epoch_abs_log_ratio"] = {"max": float(lr.max()), "mean": float(lr.mean())}
+    col["value_abs_gap_to_fp32_module"] = {"max": float(dv.max()), "mean": float(dv.mean())}
+    for p in ppos.values():
+        p.env.close()
+    doc["collect"] = col
+    rec = os.environ.get("TE_POLICY_BF16_RECORD")
+    if rec and os.path.exists(rec):
+        doc["numerics"] = [json.loads(line) for line in open(rec) if line.strip()]
+    with open(os.path.join(ROOT, "profiles", "policy_bf16.json"), "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    return doc
+
+
+if args.only_bf16:
+    print(json.dumps({"bf16": bf16_part()}, indent=1))
+    sys.exit(0)
 
 out = {"features_dim": args.features_dim, "net_arch": list(args.net_arch), "macs_per_row": MACS_PER_ROW, "forward": []}
 torch.manual_seed(0)
@@ -137,4 +232,5 @@ for ff in (False, True):
         "policy_share_of_collect": 1.0 - t_env * T / t_col}
     env.close(); del ppo
     torch.cuda.empty_cache()
+out["bf16"] = bf16_part()
 print(json.dumps(out, indent=1))
