@@ -6,7 +6,8 @@ kernel sums in another order, so it is not bit-exact); the statistics to 1e-4 |s
 gradient at a ReLU kink: a pre-activation within rounding of 0 takes the other side in the other summation order, and its row's
 dL/dY then enters the bias sum or not.  Measured on the MI355X (trained weights, te_step rows, B = 4 096): a pre-activation of 3.0e-9
 moved inertial.4.bias by 1.78e-6 = its row's dL/dY exactly, while fp32 autograd was within 1.3e-10 of fp64 there.  The measured gaps
-are printed (pytest -s)."""
+are printed (pytest -s).  The kink term is far above most tensors' norms at small B: tests/test_policy_kinkfree.py holds the same kernel to
+fp64 per element on inputs that have no kink."""
 import ctypes as C
 import hashlib
 import os
