@@ -20,6 +20,7 @@ EXPORTS = (
     "te_policy_shape_check", "te_policy_param_words_shaped", "te_policy_act_shaped", "te_drive_wingman_shaped",
     "te_policy_grad_workspace_bytes_shaped", "te_policy_ppo_grad_shaped",
     "te_policy_bf16_words", "te_policy_pack_bf16", "te_policy_act_bf16",
+    "te_policy_bf16_grad_words", "te_policy_pack_bf16_grad", "te_policy_grad_bf16_workspace_bytes", "te_policy_ppo_grad_bf16",
     "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad", "te_kernel_plan",
     "te_policy_opt_state_bytes", "te_policy_adam_step",
     "te_rollout_gae", "te_adv_stats_workspace_bytes", "te_adv_stats",
@@ -100,6 +101,10 @@ def load() -> C.CDLL:
     L.te_policy_ppo_grad.argtypes = [vp, i32, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]
     L.te_policy_grad_workspace_bytes_shaped.argtypes = [shape, i32, C.POINTER(C.c_size_t)]
     L.te_policy_ppo_grad_shaped.argtypes = [vp, shape, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]
+    L.te_policy_bf16_grad_words.argtypes = [shape, C.POINTER(C.c_size_t)]
+    L.te_policy_pack_bf16_grad.argtypes = [vp, shape, vp, vp]
+    L.te_policy_grad_bf16_workspace_bytes.argtypes = [shape, i32, C.POINTER(C.c_size_t)]
+    L.te_policy_ppo_grad_bf16.argtypes = [vp, vp, vp, shape, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]
     L.te_policy_opt_state_bytes.argtypes = [C.c_size_t, C.POINTER(C.c_size_t)]
     L.te_policy_adam_step.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t] + [C.c_double] * 4 + [f32, f32, vp]
     L.te_rollout_gae.argtypes = [i32, i32] + [vp] * 4 + [C.c_double, C.c_double, vp, vp, vp]

@@ -48,6 +48,7 @@
 #include "te_policy_bf16.hpp"
 #include "te_wingman.hpp"
 #include "te_policy_grad.hpp"
+#include "te_policy_grad_bf16.hpp"
 #include "te_policy_opt.hpp"
 #include "te_rollout.hpp"
 #include "te_monitor.hpp"
@@ -1124,6 +1125,37 @@ static int policy_launch_bf16(int shape_id, int32_t lidar_channels, const float*
   return 0;
 }
 
+// te_policy_ppo_grad_bf16's tile kernel (te_policy_grad_bf16.hpp): its own LDS plan, both bf16 weight buffers
+using PolGradBf16Kernel = void (*)(PolicyParams, PolicyBf16, PolicyBf16, PolicyIn, GradTileArgsB);
+static const PolGradBf16Kernel kPolicyGradBf16Kernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_grad_bf16_tile_kernel);
+
+static int policy_launch_grad_bf16(int shape_id, int32_t lidar_channels, const float* params, const uint16_t* weights, const uint16_t* weights_t,
+                                   int rows, void* stream, const PolicyIn& in, const GradTileArgsB& t) {
+  static std::map<const void*, uint64_t> opted;
+  static std::mutex opted_lock;
+  const PolShape shape = pol_shape(shape_id, lidar_channels);
+  const PolGradLdsB lds = pol_grad_lds_plan_bf16(shape);
+  const PolGradBf16Kernel fn = kPolicyGradBf16Kernels[shape_id][lidar_channels - 2];
+  int dev = 0;
+  TE_HIP(hipGetDevice(&dev));
+  {
+    std::lock_guard<std::mutex> hold(opted_lock);
+    uint64_t& bits = opted[reinterpret_cast<const void*>(fn)];
+    if (dev < 64 && !(bits >> dev & 1)) {
+      TE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes));
+      bits |= 1ull << dev;
+    }
+  }
+  PolicyParams P = policy_layout(shape);
+  P.base = params;
+  PolicyBf16 W = policy_bf16_layout(shape), Wt = policy_bf16_t_layout(shape);
+  W.base = weights;
+  Wt.base = weights_t;
+  hipLaunchKernelGGL(fn, dim3((unsigned)(rows / lds.M)), dim3(lds.threads), (size_t)lds.bytes, (hipStream_t)stream, P, W, Wt, in, t);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
 static std::string shape_text(const PolShape& s) {
   std::string t = "features_dim " + std::to_string(s.F) + ", hidden";
   for (int i = 0; i < s.n_hidden; ++i) t += (i ? ", " : " ") + std::to_string(s.h[i]);
@@ -1970,6 +2002,82 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad_shaped(const float
   return policy_ppo_grad("te_policy_ppo_grad_shaped", "te_policy_grad_workspace_bytes_shaped", id, params, shape->lidar_channels, n, index,
                          lidar, inertial, last_action, action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef, grad, stats,
                          workspace, workspace_bytes, stream);
+}
+
+// ---- te_policy_ppo_grad_bf16 (te_policy_grad_bf16.hpp)
+__attribute__((visibility("default"))) int te_policy_bf16_grad_words(const te_policy_shape* shape, size_t* out_halfwords) {
+  if (!out_halfwords) return fail("te_policy_bf16_grad_words: null argument");
+  const int id = policy_shape_id(shape, "te_policy_bf16_grad_words");
+  if (id < 0) return 1;
+  *out_halfwords = (size_t)policy_bf16_t_layout(pol_shape(id, shape->lidar_channels)).words;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_pack_bf16_grad(const float* params, const te_policy_shape* shape, uint16_t* out, void* stream) {
+  const int id = policy_shape_id(shape, "te_policy_pack_bf16_grad");
+  if (id < 0) return 1;
+  if (!params || !out) return fail("te_policy_pack_bf16_grad: null argument");
+  if ((uintptr_t)params & 15) return fail("te_policy_pack_bf16_grad: params must be 16-byte aligned");
+  if ((uintptr_t)out & 15) return fail("te_policy_pack_bf16_grad: out must be 16-byte aligned");
+  const PolPackTPlan plan = policy_pack_t_plan(pol_shape(id, shape->lidar_channels));
+  hipLaunchKernelGGL(policy_pack_bf16_t_kernel, dim3((unsigned)((plan.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, plan,
+                     reinterpret_cast<__bf16*>(out));
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_grad_bf16_workspace_bytes(const te_policy_shape* shape, int32_t n, size_t* out_bytes) {
+  if (!out_bytes) return fail("te_policy_grad_bf16_workspace_bytes: null argument");
+  const int id = policy_shape_id(shape, "te_policy_grad_bf16_workspace_bytes");
+  if (id < 0) return 1;
+  if (policy_grad_rows_check("te_policy_grad_bf16_workspace_bytes", n)) return 1;
+  const PolShape sh = pol_shape(id, shape->lidar_channels);
+  *out_bytes = policy_grad_bf16_layout(sh, n, nullptr, policy_layout(sh), nullptr, nullptr, nullptr, nullptr);
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_ppo_grad_bf16(const float* params, const uint16_t* weights_bf16, const uint16_t* weights_bf16_t,
+                                                                   const te_policy_shape* shape, int32_t n, const int64_t* index,
+                                                                   const float* lidar, const float* inertial, const float* last_action,
+                                                                   const float* action, const float* old_logp, const float* adv, const float* ret,
+                                                                   const float* adv_mean_std, float clip_range, float vf_coef, float ent_coef,
+                                                                   float* grad, float* stats, void* workspace, size_t workspace_bytes,
+                                                                   void* stream) {
+  const std::string who = "te_policy_ppo_grad_bf16";
+  const int id = policy_shape_id(shape, "te_policy_ppo_grad_bf16");
+  if (id < 0) return 1;
+  if (policy_grad_rows_check(who, n)) return 1;
+  if (!params || !weights_bf16 || !weights_bf16_t || !lidar || !inertial || !last_action || !action || !old_logp || !adv || !ret || !grad ||
+      !stats || !workspace)
+    return fail(who + ": null argument");
+  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if ((uintptr_t)weights_bf16 & 15) return fail(who + ": weights_bf16 must be 16-byte aligned");
+  if ((uintptr_t)weights_bf16_t & 15) return fail(who + ": weights_bf16_t must be 16-byte aligned");
+  if ((uintptr_t)grad & 15) return fail(who + ": grad must be 16-byte aligned");
+  if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
+  if ((uintptr_t)workspace & 255) return fail(who + ": workspace must be 256-byte aligned");
+  if ((uintptr_t)index & 7) return fail(who + ": index must be 8-byte aligned");
+  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)action, (const void*)old_logp, (const void*)adv,
+                        (const void*)ret, (const void*)adv_mean_std, (const void*)stats})
+    if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
+  GradTileArgsB t; GradPlan g;
+  const PolShape sh = pol_shape(id, shape->lidar_channels);
+  const size_t need = policy_grad_bf16_layout(sh, n, static_cast<char*>(workspace), policy_layout(sh), grad, stats, &t, &g);
+  if (workspace_bytes < need)
+    return fail(who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_policy_grad_bf16_workspace_bytes says " +
+                std::to_string(need) + ")");
+  if (!std::isfinite(clip_range) || clip_range < 0.f) return fail(who + ": clip_range must be finite and >= 0");
+  t.action = action; t.old_logp = old_logp; t.adv = adv; t.ret = ret; t.adv_mean_std = adv_mean_std;
+  t.clip = clip_range; t.vf_coef = vf_coef; t.ent_coef = ent_coef; t.inv_n = 1.f / (float)n;
+  const PolicyIn in{lidar, inertial, last_action, index, n};
+  const hipStream_t s = (hipStream_t)stream;
+  // the tile grid covers the workspace's Bp rows (n rounded up to the tile): a padding row writes its zeros like any other
+  if (policy_launch_grad_bf16(id, shape->lidar_channels, params, weights_bf16, weights_bf16_t, t.Bp, stream, in, t)) return 1;
+  hipLaunchKernelGGL(policy_wgrad_bf16_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
+  TE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
+  TE_HIP(hipGetLastError());
+  return 0;
 }
 
 // ---- optimiser step (te_policy_opt.hpp): every check is on the host, before any launch

@@ -30,11 +30,16 @@
 //   F = 512 shapes: 48 rows, 512 threads (8 waves), 141.2 KB: Z + F + the 512-wide head tile at 64 rows would be 191 KB.  Every
 //                  workgroup reads all 1.5 / 2.1 MB of bf16 weights for 48 rows, a sixth of the bytes per row of the fp32 kernel's
 //                  16-row tile, and the CU holds two waves per SIMD.
+//
+// The forward itself is pol_forward_bf16<C, S, M>(..., save): the kernel below calls it with a hook that saves nothing, and
+// te_policy_grad_bf16.hpp's tile kernel with one that writes every layer's input to its workspace and with a tile height of its own (the
+// outputs of a row do not depend on it), so the gradient's forward is this one bit for bit.
 #pragma once
 
 namespace te {
 
 typedef __bf16 pol_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 pol_bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPolBPad = 8;                    // bf16 elements (16 bytes) behind every LDS row
 constexpr int kPolBZS = 448 + kPolBPad;        // LDS row strides in bf16 elements
@@ -97,15 +102,16 @@ __global__ __launch_bounds__(256) void policy_pack_bf16_kernel(const float* __re
 // val in floats from the start; bytes in all.  Z [M][kPolBZS] at 0, T1 and T2 [M][kPolBTS] behind it; the trunk F [M][fs] over T1 / T2
 // (dead by then) and beyond; the heads' tiles B [M][bs] (hidden layer 1) at 0 and A [M][as] (hidden layers 0 and 2) behind B, both
 // over the dead Z, when they fit it (default shape), else A behind F; MU [M][4] and VAL [M] in fp32 behind everything.
+// tile_m: another tile height for the same map (te_policy_grad_bf16.hpp runs this forward at 32 rows for every shape); 0: the inference's.
 struct PolLdsB { int M, threads, t1, t2, f, fs, a, as, b, bs, mu, val, bytes; };
 
 __host__ __device__ constexpr int pol_max(int a, int b) { return a > b ? a : b; }
 
-__host__ __device__ constexpr PolLdsB pol_lds_plan_bf16(PolShape S) {
+__host__ __device__ constexpr PolLdsB pol_lds_plan_bf16(PolShape S, int tile_m = 0) {
   const int h1 = S.n_hidden > 1 ? S.h[1] : 0, h2 = S.n_hidden > 2 ? S.h[2] : 0;
   const int fs = S.F + kPolBPad, as = pol_max(S.h[0], h2) + kPolBPad, bs = h1 + kPolBPad;
   const bool wide = S.F > 256;
-  const int M = wide ? 48 : 32, threads = wide ? 512 : 256;
+  const int M = tile_m ? tile_m : (wide ? 48 : 32), threads = wide ? 512 : 256;
   const int t1 = M * kPolBZS, t2 = t1 + M * kPolBTS, f = t1;
   const int a = bs + as <= kPolBZS ? M * bs : f + M * fs;
   const int end = pol_max(pol_max(t2 + M * kPolBTS, f + M * fs), a + M * as);
@@ -115,8 +121,8 @@ __host__ __device__ constexpr PolLdsB pol_lds_plan_bf16(PolShape S) {
 
 // A plan is sound when nothing lies over a live tile: F clear of Z (the trunk reads Z), B within the dead Z and clear of A and F,
 // A clear of B and F (F stays live through both heads), MU / VAL behind every tile, every tile 16-byte aligned, all within the CU.
-__host__ __device__ constexpr bool pol_lds_bf16_ok(PolShape S) {
-  const PolLdsB p = pol_lds_plan_bf16(S);
+__host__ __device__ constexpr bool pol_lds_bf16_ok(PolShape S, int tile_m = 0) {
+  const PolLdsB p = pol_lds_plan_bf16(S, tile_m);
   const int z_end = p.M * kPolBZS, f_end = p.f + p.M * p.fs, a_end = p.a + p.M * p.as, b_end = p.b + p.M * p.bs;
   return p.bytes <= kPolLdsLimit && p.M % 16 == 0 && p.M <= p.threads && p.threads % 64 == 0 && p.threads <= 1024 &&
          p.t1 >= z_end && p.t2 >= p.t1 + p.M * kPolBTS && p.f >= z_end && b_end <= z_end && b_end <= p.f &&
@@ -135,10 +141,13 @@ static_assert(pol_lds_bf16_ok(pol_shape(POL_SHAPE_LEARN, 3)) && pol_lds_plan_bf1
 // of column n; epi(row, col, value) consumes one fp32 output element.  Lane l of a 16 x 16 tile (r = l & 15, h = l >> 4):
 // A = X[r][k0 + 8 h + j], B = W[n0 + r][k0 + 8 h + j], j = 0..7: one 16-byte load each; C/D: column r, rows 4 h .. 4 h + 3 (pol_gemm's).
 // Wave w of NW owns the 16-column slices w, w + NW, ... for all MT row tiles: one weight load feeds MT MFMAs.
-template <int K, int N, int MT, int NW, class Init, class Epi>
-TE_DEV void pol_gemm_bf16(const __bf16* X, int ldx, const __bf16* __restrict__ W, Init init, Epi epi) {
+// epi(m0, n, v) takes the four rows m0 .. m0 + 3 a lane holds of column n.  K2 > 0: a second operand pair, X2 [.][K2] and W2 [N][K2p],
+// runs into the same accumulator behind the first (the trunk's gradient over both heads, te_policy_grad_bf16.hpp).
+template <int K, int N, int MT, int NW, int K2 = 0, class Init, class Epi>
+TE_DEV void pol_gemm_bf16(const __bf16* X, int ldx, const __bf16* __restrict__ W, Init init, Epi epi, const __bf16* X2 = nullptr, int ldx2 = 0,
+                          const __bf16* __restrict__ W2 = nullptr) {
   static_assert(N % 16 == 0, "whole 16-column slices");
-  constexpr int Kp = pol_kp(K);
+  constexpr int Kp = pol_kp(K), K2p = pol_kp(K2);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, h = lane >> 4;
   for (int nt = wave; nt < N / 16; nt += NW) {
     const int n = nt * 16 + r;
@@ -157,62 +166,97 @@ TE_DEV void pol_gemm_bf16(const __bf16* X, int ldx, const __bf16* __restrict__ W
 #pragma unroll
       for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], w, acc[t], 0, 0, 0);
     }
+    if constexpr (K2 > 0) {
+      const __bf16* wr2 = W2 + (size_t)n * K2p + 8 * h;
+      const __bf16* xr2 = X2 + r * ldx2 + 8 * h;
+#pragma unroll 8
+      for (int k0 = 0; k0 < K2p; k0 += 32) {
+        const pol_bf16x8 w = *reinterpret_cast<const pol_bf16x8*>(wr2 + k0);
+        pol_bf16x8 a[MT];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int t = 0; t < MT; ++t) a[t] = *reinterpret_cast<const pol_bf16x8*>(xr2 + 16 * t * ldx2 + k0);
 #pragma unroll
-      for (int t = 0; t < MT; ++t) epi(16 * t + 4 * h + i, n, acc[t][i]);
+        for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], w, acc[t], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < MT; ++t) epi(16 * t + 4 * h, n, acc[t]);
   }
 }
 
-// The forward of weight layer L of shape S: Y = act(X W^T + b) with W from the bf16 buffer and b from the fp32 one; the fp32 result
-// is rounded to bf16 where store(row, col) points.
-template <int L, int C, int S, int ACT, class At>
-TE_DEV void pol_linear_bf16(const PolicyParams& P, const PolicyBf16& Wb, const __bf16* X, int ldx, At at) {
+// The forward of weight layer L of shape S on an M-row tile: Y = act(X W^T + b) with W from the bf16 buffer and b from the fp32 one; the
+// fp32 result is rounded to bf16 and handed to store(m0, n, y): rows m0 .. m0 + 3 of column n.
+template <int L, int C, int S, int ACT, int M, class Store>
+TE_DEV void pol_linear_bf16(const PolicyParams& P, const PolicyBf16& Wb, const __bf16* X, int ldx, Store store) {
   constexpr PolLayer y = pol_layer(L, pol_shape(S, C));
-  constexpr PolLdsB lp = pol_lds_plan_bf16(pol_shape(S, C));
+  constexpr PolLdsB lp = pol_lds_plan_bf16(pol_shape(S, C), M);
   const float* __restrict__ bias = P.base + P.at[L].b;
   pol_gemm_bf16<y.K, y.N, lp.M / 16, lp.threads / 64>(
       X, ldx, reinterpret_cast<const __bf16*>(Wb.base) + Wb.at[L], [=](int n) { return bias[n]; },
-      [=](int m, int n, float v) { *at(m, n) = (__bf16)(ACT == POL_RELU ? fmaxf(v, 0.f) : tanhf(v)); });
+      [=](int m0, int n, pol_f32x4 v) {
+        pol_bf16x4 o;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = (__bf16)(ACT == POL_RELU ? fmaxf(v[i], 0.f) : tanhf(v[i]));
+        store(m0, n, o);
+      });
 }
 
+// What pol_forward_bf16 hands to its `save` hook besides keeping it in LDS: every layer's input as the bf16 values the MFMA consumes
+// (the buffers of te_policy.hpp's POL_SV_ list).  x4: rows m0 .. m0 + 3 of column col (conv position sub); x1: one element.
+struct PolNoSaveB {
+  TE_DEV void x4(int, int, int, int, pol_bf16x4) const {}
+  TE_DEV void x1(int, int, int, int, __bf16) const {}
+};
+
+// rows m0 .. m0 + 3 of one column of an LDS tile with row stride ld
+TE_DEV void pol_tile_put4(__bf16* p, int ld, pol_bf16x4 v) { p[0] = v[0]; p[ld] = v[1]; p[2 * ld] = v[2]; p[3 * ld] = v[3]; }
+
 // One head: hidden layers L0, L0 + 1, L0 + 2 (those the shape has) with tanh, F -> A -> B -> A; returns the last one's output.
-template <int L0, int C, int S>
-TE_DEV const __bf16* pol_head_bf16(const PolicyParams& P, const PolicyBf16& Wb, const __bf16* F, __bf16* A, __bf16* B) {
+template <int L0, int C, int S, int M, class Save>
+TE_DEV const __bf16* pol_head_bf16(const PolicyParams& P, const PolicyBf16& Wb, const __bf16* F, __bf16* A, __bf16* B, Save save) {
   constexpr PolShape sh = pol_shape(S, C);
-  constexpr PolLdsB lp = pol_lds_plan_bf16(sh);
-  pol_linear_bf16<L0, C, S, POL_TANH>(P, Wb, F, lp.fs, [=](int m, int n) { return A + m * lp.as + n; });
+  constexpr PolLdsB lp = pol_lds_plan_bf16(sh, M);
+  constexpr int last = L0 == POL_L_PI0 ? POL_L_MU : POL_L_V;
+  // next: the layer that reads this output, from its saved buffer
+  auto to = [=](__bf16* Y, int ld, int next) {
+    return [=](int m0, int n, pol_bf16x4 y) { pol_tile_put4(Y + m0 * ld + n, ld, y); save.x4(pol_layer(next, sh).x, m0, 0, n, y); };
+  };
+  pol_linear_bf16<L0, C, S, POL_TANH, M>(P, Wb, F, lp.fs, to(A, lp.as, sh.n_hidden > 1 ? L0 + 1 : last));
   __syncthreads();
   if constexpr (sh.n_hidden > 1) {
-    pol_linear_bf16<L0 + 1, C, S, POL_TANH>(P, Wb, A, lp.as, [=](int m, int n) { return B + m * lp.bs + n; });
+    pol_linear_bf16<L0 + 1, C, S, POL_TANH, M>(P, Wb, A, lp.as, to(B, lp.bs, sh.n_hidden > 2 ? L0 + 2 : last));
     __syncthreads();
   }
   if constexpr (sh.n_hidden > 2) {
-    pol_linear_bf16<L0 + 2, C, S, POL_TANH>(P, Wb, B, lp.bs, [=](int m, int n) { return A + m * lp.as + n; });
+    pol_linear_bf16<L0 + 2, C, S, POL_TANH, M>(P, Wb, B, lp.bs, to(A, lp.as, last));
     __syncthreads();
   }
   return sh.n_hidden == 2 ? B : A;
 }
 
-template <int C, int S>
-__global__ __launch_bounds__(pol_lds_plan_bf16(pol_shape(S, C)).threads) void policy_act_bf16_kernel(PolicyParams P, PolicyBf16 Wb, PolicyIO io) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char pol_lds_b[];
+// The forward of the tile's M rows from row0 (rows >= in.n read zeros; row i is read at in.index[i], NULL: at i): mu and value of every
+// row into MU [M][4] and VAL [M] of pol_lds_plan_bf16(S, M) (fp32); each layer's input also goes to save.  Thread tid < M computes row
+// tid's mu and value and may read them back without a barrier.  te_policy_act_bf16 and te_policy_ppo_grad_bf16 both run this: their
+// forwards are bitwise one.  M = 0: the inference's tile height.
+template <int C, int S, int M = 0, class Save>
+TE_DEV void pol_forward_bf16(const PolicyParams& P, const PolicyBf16& Wb, const PolicyIn& in, unsigned char* pol_lds_b, int row0, Save save) {
   constexpr PolShape sh = pol_shape(S, C);
-  constexpr PolLdsB lp = pol_lds_plan_bf16(sh);
-  constexpr int M = lp.M, MT = M / 16, NT = lp.threads, NW = NT / 64;
+  constexpr PolLdsB lp = pol_lds_plan_bf16(sh, M);
+  static_assert(pol_lds_bf16_ok(sh, M), "the tile height fits the shape");
+  constexpr int TM = lp.M, MT = TM / 16, NT = lp.threads, NW = NT / 64;
   __bf16* lds = reinterpret_cast<__bf16*>(pol_lds_b);
-  __bf16* Z = lds;                             // [M][kPolBZS]: lidar 0..191 | inertial 192..319 | last_action 320..447
-  __bf16* T1 = lds + lp.t1;                    // [M][kPolBTS]
-  __bf16* T2 = lds + lp.t2;                    // [M][kPolBTS]
-  __bf16* F = lds + lp.f;                      // [M][lp.fs] once T1 / T2 are dead
-  __bf16* HA = lds + lp.a;                     // [M][lp.as], [M][lp.bs]
+  __bf16* Z = lds;                             // [TM][kPolBZS]: lidar 0..191 | inertial 192..319 | last_action 320..447
+  __bf16* T1 = lds + lp.t1;                    // [TM][kPolBTS]
+  __bf16* T2 = lds + lp.t2;                    // [TM][kPolBTS]
+  __bf16* F = lds + lp.f;                      // [TM][lp.fs] once T1 / T2 are dead
+  __bf16* HA = lds + lp.a;                     // [TM][lp.as], [TM][lp.bs]
   __bf16* HB = lds + lp.b;
-  float* MU = reinterpret_cast<float*>(pol_lds_b) + lp.mu;     // [M][4]
-  float* VAL = reinterpret_cast<float*>(pol_lds_b) + lp.val;   // [M]
+  float* MU = reinterpret_cast<float*>(pol_lds_b) + lp.mu;     // [TM][4]
+  float* VAL = reinterpret_cast<float*>(pol_lds_b) + lp.val;   // [TM]
   const float* __restrict__ prm = P.base;
   const __bf16* __restrict__ wb = reinterpret_cast<const __bf16*>(Wb.base);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, h = lane >> 4;
-  const int row0 = blockIdx.x * M;
+  auto src = [&](int row) -> size_t { return in.index ? (size_t)in.index[row] : (size_t)row; };
 
   // ---- LIDAR: conv1 + conv2, one conv2 output column (ow2) at a time.  conv1's k = c * 16 + kh * 4 + kw: k-block kb of 32 holds
   // channels 2 kb and 2 kb + 1, lane group h the patch rows kh = 2 (h & 1), + 1 of channel 2 kb + (h >> 1); a channel >= C is the
@@ -234,57 +278,80 @@ __global__ __launch_bounds__(pol_lds_plan_bf16(pol_shape(S, C)).threads) void po
         for (int t = 0; t < MT; ++t) {
           const int row = row0 + 16 * t + r;
           float2 p0 = make_float2(0.f, 0.f), p1 = p0, p2 = p0, p3 = p0;
-          if (c < C && row < io.n) {
-            const float* s = io.lidar + ((size_t)row * C + c) * (13 * 26) + (4 * oh + kh) * 26 + 4 * ow;
+          if (c < C && row < in.n) {
+            const float* s = in.lidar + (src(row) * C + c) * (13 * 26) + (4 * oh + kh) * 26 + 4 * ow;
             p0 = *reinterpret_cast<const float2*>(s);      p1 = *reinterpret_cast<const float2*>(s + 2);
             p2 = *reinterpret_cast<const float2*>(s + 26); p3 = *reinterpret_cast<const float2*>(s + 28);
           }
           a[t] = pol_bf16x8{(__bf16)p0.x, (__bf16)p0.y, (__bf16)p1.x, (__bf16)p1.y, (__bf16)p2.x, (__bf16)p2.y, (__bf16)p3.x, (__bf16)p3.y};
+          if (nt == 0 && c < C) {      // the patch as the MFMA reads it: column kb * 32 + 8 h + e = c * 16 + kh * 4 + kw
+#pragma unroll
+            for (int e = 0; e < 8; ++e) save.x1(POL_SV_C1X, 16 * t + r, ow2 * 4 + oh * 2 + j, kb * 32 + 8 * h + e, a[t][e]);
+          }
         }
 #pragma unroll
         for (int t = 0; t < MT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], w, acc[t], 0, 0, 0);
       }
       // conv1 output (row, co, oh, ow) -> conv2 patch of column ow2: T1[row][co * 4 + oh * 2 + j]
 #pragma unroll
-      for (int t = 0; t < MT; ++t)
+      for (int t = 0; t < MT; ++t) {
+        pol_bf16x4 o;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) T1[(16 * t + 4 * h + i) * kPolBTS + n * 4 + oh * 2 + j] = (__bf16)fmaxf(acc[t][i], 0.f);
+        for (int i = 0; i < 4; ++i) o[i] = (__bf16)fmaxf(acc[t][i], 0.f);
+        pol_tile_put4(T1 + (16 * t + 4 * h) * kPolBTS + n * 4 + oh * 2 + j, kPolBTS, o);
+        save.x4(POL_SV_C2X, 16 * t + 4 * h, ow2, n * 4 + oh * 2 + j, o);
+      }
     }
     __syncthreads();
-    pol_linear_bf16<POL_L_C2, C, S, POL_RELU>(P, Wb, T1, kPolBTS, [=](int m, int n) { return Z + m * kPolBZS + n * 3 + ow2; });
+    pol_linear_bf16<POL_L_C2, C, S, POL_RELU, M>(P, Wb, T1, kPolBTS, [=](int m0, int n, pol_bf16x4 y) {
+      pol_tile_put4(Z + m0 * kPolBZS + n * 3 + ow2, kPolBZS, y);
+      save.x4(POL_SV_FX, m0, 0, n * 3 + ow2, y);
+    });
     __syncthreads();
   }
 
   // ---- inertial_data [15] and last_action [4], zero-padded to one k-block of 32, through 3 x (Linear(128) + ReLU) each
-  for (int t = tid; t < M * 32; t += NT) {
+  for (int t = tid; t < TM * 32; t += NT) {
     const int m = t >> 5, k = t & 31, row = row0 + m;
-    T1[m * kPolBTS + k] = (__bf16)((row < io.n && k < 15) ? io.inertial[(size_t)row * 15 + k] : 0.f);
-    T2[m * kPolBTS + k] = (__bf16)((row < io.n && k < 4) ? io.last_action[(size_t)row * 4 + k] : 0.f);
+    const __bf16 vi = (__bf16)((row < in.n && k < 15) ? in.inertial[src(row) * 15 + k] : 0.f);
+    const __bf16 va = (__bf16)((row < in.n && k < 4) ? in.last_action[src(row) * 4 + k] : 0.f);
+    T1[m * kPolBTS + k] = vi;
+    T2[m * kPolBTS + k] = va;
+    if (k < 15) save.x1(POL_SV_IN0X, m, 0, k, vi);
+    if (k < 4) save.x1(POL_SV_AC0X, m, 0, k, va);
   }
   __syncthreads();
   // each chain ping-pongs between its own 128 columns of Z and its own tile (inertial: T1, last_action: T2); the two chains share
-  // nothing, so layer i of both runs between one pair of barriers
-  auto toZ = [=](int col0) { return [=](int m, int n) { return Z + m * kPolBZS + col0 + n; }; };
-  auto toT = [=](__bf16* T) { return [=](int m, int n) { return T + m * kPolBTS + n; }; };
-  pol_linear_bf16<POL_L_IN0, C, S, POL_RELU>(P, Wb, T1, kPolBTS, toZ(192));
-  pol_linear_bf16<POL_L_AC0, C, S, POL_RELU>(P, Wb, T2, kPolBTS, toZ(320));
+  // nothing, so layer i of both runs between one pair of barriers.  next: the layer that reads the output, from its saved buffer
+  auto toZ = [=](int col0, int next) {
+    const int sv = pol_layer(next, sh).x;
+    return [=](int m0, int n, pol_bf16x4 y) { pol_tile_put4(Z + m0 * kPolBZS + col0 + n, kPolBZS, y); save.x4(sv, m0, 0, sv == POL_SV_FX ? col0 + n : n, y); };
+  };
+  auto toT = [=](__bf16* T, int next) {
+    return [=](int m0, int n, pol_bf16x4 y) { pol_tile_put4(T + m0 * kPolBTS + n, kPolBTS, y); save.x4(pol_layer(next, sh).x, m0, 0, n, y); };
+  };
+  pol_linear_bf16<POL_L_IN0, C, S, POL_RELU, M>(P, Wb, T1, kPolBTS, toZ(192, POL_L_IN1));
+  pol_linear_bf16<POL_L_AC0, C, S, POL_RELU, M>(P, Wb, T2, kPolBTS, toZ(320, POL_L_AC1));
   __syncthreads();
-  pol_linear_bf16<POL_L_IN1, C, S, POL_RELU>(P, Wb, Z + 192, kPolBZS, toT(T1));
-  pol_linear_bf16<POL_L_AC1, C, S, POL_RELU>(P, Wb, Z + 320, kPolBZS, toT(T2));
+  pol_linear_bf16<POL_L_IN1, C, S, POL_RELU, M>(P, Wb, Z + 192, kPolBZS, toT(T1, POL_L_IN2));
+  pol_linear_bf16<POL_L_AC1, C, S, POL_RELU, M>(P, Wb, Z + 320, kPolBZS, toT(T2, POL_L_AC2));
   __syncthreads();
-  pol_linear_bf16<POL_L_IN2, C, S, POL_RELU>(P, Wb, T1, kPolBTS, toZ(192));
-  pol_linear_bf16<POL_L_AC2, C, S, POL_RELU>(P, Wb, T2, kPolBTS, toZ(320));
+  pol_linear_bf16<POL_L_IN2, C, S, POL_RELU, M>(P, Wb, T1, kPolBTS, toZ(192, POL_L_F));
+  pol_linear_bf16<POL_L_AC2, C, S, POL_RELU, M>(P, Wb, T2, kPolBTS, toZ(320, POL_L_F));
   __syncthreads();
 
   // ---- trunk: concat [448] -> Linear(F) + ReLU
-  pol_linear_bf16<POL_L_F, C, S, POL_RELU>(P, Wb, Z, kPolBZS, [=](int m, int n) { return F + m * lp.fs + n; });
+  pol_linear_bf16<POL_L_F, C, S, POL_RELU, M>(P, Wb, Z, kPolBZS, [=](int m0, int n, pol_bf16x4 y) {
+    pol_tile_put4(F + m0 * lp.fs + n, lp.fs, y);
+    save.x4(POL_SV_F, m0, 0, n, y);
+  });
   __syncthreads();
 
   // ---- pi head, then mu; vf head, then value (one thread per row: the thread that wrote MU and VAL reads them back, no barrier)
   constexpr int KL = pol_layer(POL_L_MU, sh).K, ls = sh.n_hidden == 2 ? lp.bs : lp.as;
-  const __bf16* PX = pol_head_bf16<POL_L_PI0, C, S>(P, Wb, F, HA, HB);
+  const __bf16* PX = pol_head_bf16<POL_L_PI0, C, S, M>(P, Wb, F, HA, HB, save);
   static_assert(KL % 8 == 0, "the last hidden tile is read 8 elements at a time");
-  if (tid < M) {      // every sum runs over k in order; one 16-byte LDS read feeds 8 k of all four
+  if (tid < TM) {      // every sum runs over k in order; one 16-byte LDS read feeds 8 k of all four
     float s[4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) s[a] = prm[P.at[POL_L_MU].b + a];
@@ -299,9 +366,8 @@ __global__ __launch_bounds__(pol_lds_plan_bf16(pol_shape(S, C)).threads) void po
     for (int a = 0; a < 4; ++a) MU[tid * 4 + a] = s[a];
   }
   __syncthreads();
-  const __bf16* VX = pol_head_bf16<POL_L_VF0, C, S>(P, Wb, F, HA, HB);
-  const int row = row0 + tid;
-  if (tid < M) {
+  const __bf16* VX = pol_head_bf16<POL_L_VF0, C, S, M>(P, Wb, F, HA, HB, save);
+  if (tid < TM) {
     float v = prm[P.at[POL_L_V].b];
     for (int k0 = 0; k0 < KL; k0 += 8) {
       const pol_bf16x8 x = *reinterpret_cast<const pol_bf16x8*>(VX + tid * ls + k0);
@@ -310,7 +376,19 @@ __global__ __launch_bounds__(pol_lds_plan_bf16(pol_shape(S, C)).threads) void po
     }
     VAL[tid] = v;
   }
-  // ---- policy_act_kernel's tail
+}
+
+template <int C, int S>
+__global__ __launch_bounds__(pol_lds_plan_bf16(pol_shape(S, C)).threads) void policy_act_bf16_kernel(PolicyParams P, PolicyBf16 Wb, PolicyIO io) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pol_lds_b[];
+  constexpr PolLdsB lp = pol_lds_plan_bf16(pol_shape(S, C));
+  constexpr int M = lp.M;
+  const PolicyIn in{io.lidar, io.inertial, io.last_action, nullptr, io.n};
+  const int tid = threadIdx.x, row = blockIdx.x * M + tid;
+  pol_forward_bf16<C, S>(P, Wb, in, pol_lds_b, blockIdx.x * M, PolNoSaveB{});
+  // ---- policy_act_kernel's tail: the outputs of the row, read back by the thread that computed them
+  const float* MU = reinterpret_cast<const float*>(pol_lds_b) + lp.mu;
+  const float* VAL = reinterpret_cast<const float*>(pol_lds_b) + lp.val;
   const float* log_std = P.base + P.log_std;
   if (tid < M && row < io.n) {
     io.value[row] = VAL[tid];

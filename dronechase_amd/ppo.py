@@ -236,13 +236,19 @@ class FusedPolicy:
     After bind_parameters() the module's parameters are views of the packed buffer and there is nothing left to repack.
     precision="bf16": forward and act go to te_policy_act_bf16 (bf16 operands on the bf16 MFMA, fp32 accumulation; the numerics
     contract is in include/threatengage.h).  The object then owns a second buffer, the weights rounded to bf16 (te_policy_pack_bf16),
-    at a stable address too; refresh() repacks it with one more launch, also after bind_parameters().  ppo_grad is untouched: it
-    reads the fp32 buffer."""
+    at a stable address too; refresh() repacks it with one more launch, also after bind_parameters().  precision does not touch
+    ppo_grad.
+    grad_precision="bf16": ppo_grad goes to te_policy_ppo_grad_bf16 (the same contract, extended to the backward), whose forward is
+    bitwise te_policy_act_bf16's.  The object then owns weights_bf16 (shared with precision="bf16") and weights_bf16_t, the transposed
+    rounded weights (te_policy_pack_bf16_grad), both at stable addresses and both repacked by refresh(), also when bound.  forward and
+    act follow `precision` alone: precision="fp32", grad_precision="bf16" keeps the fp32 forward."""
 
-    def __init__(self, policy: nn.Module, precision: str = "fp32"):
+    def __init__(self, policy: nn.Module, precision: str = "fp32", grad_precision: str = "fp32"):
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"FusedPolicy: precision must be 'fp32' or 'bf16', not {precision!r}")
-        self.precision = precision
+        if grad_precision not in ("fp32", "bf16"):
+            raise ValueError(f"FusedPolicy: grad_precision must be 'fp32' or 'bf16', not {grad_precision!r}")
+        self.precision, self.grad_precision = precision, grad_precision
         self.policy = policy
         self.lidar_channels, self.features_dim, self.net_arch = policy_shape(policy)
         params = _packed_order(policy)
@@ -254,11 +260,14 @@ class FusedPolicy:
         if sum(p.numel() for p in params) != words:
             raise ValueError(f"policy has {sum(p.numel() for p in params)} parameters, te_policy_act's layout {words}: not a LidarInertialActionPolicy")
         self.params = torch.empty(words, dtype=torch.float32, device=self.device)
-        self.weights_bf16 = None
-        if precision == "bf16":
-            half = C.c_size_t()
+        self.weights_bf16 = self.weights_bf16_t = None
+        half = C.c_size_t()
+        if precision == "bf16" or grad_precision == "bf16":
             _lib.check(_lib.load().te_policy_bf16_words(C.byref(self.shape), C.byref(half)), "te_policy_bf16_words")
             self.weights_bf16 = torch.empty(int(half.value), dtype=torch.int16, device=self.device)
+        if grad_precision == "bf16":
+            _lib.check(_lib.load().te_policy_bf16_grad_words(C.byref(self.shape), C.byref(half)), "te_policy_bf16_grad_words")
+            self.weights_bf16_t = torch.empty(int(half.value), dtype=torch.int16, device=self.device)
         self.bound = False
         self.refresh()
 
@@ -270,6 +279,9 @@ class FusedPolicy:
                 stream = torch.cuda.current_stream(self.device).cuda_stream
                 _lib.check(_lib.load().te_policy_pack_bf16(self.params.data_ptr(), C.byref(self.shape), self.weights_bf16.data_ptr(), stream),
                            "te_policy_pack_bf16")
+                if self.weights_bf16_t is not None:
+                    _lib.check(_lib.load().te_policy_pack_bf16_grad(self.params.data_ptr(), C.byref(self.shape), self.weights_bf16_t.data_ptr(),
+                                                                    stream), "te_policy_pack_bf16_grad")
 
     @torch.no_grad()
     def bind_parameters(self) -> None:
@@ -311,7 +323,8 @@ class FusedPolicy:
         no host synchronisation; for the default shape bitwise te_policy_ppo_grad.  The workspace (per row 17 280 B for the default
         shape, 31 616 B for features_dim 512 with net_arch (128, 256, 512) or (512, 128, 256), at 3 LIDAR channels; plus the split-K
         partials: 17.8 KB and 33.2 / 33.7 KB per row in all at 65 536 rows) is owned here and grows on demand, which a capturing stream does not allow:
-        make the first call of a size outside capture."""
+        make the first call of a size outside capture.  grad_precision="bf16": one te_policy_ppo_grad_bf16 call instead, the same
+        arguments and outputs, a workspace of about half the size."""
         lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
         m = lidar.shape[0]
         b = m if index is None else index.shape[0]
@@ -330,7 +343,11 @@ class FusedPolicy:
             raise ValueError("FusedPolicy.ppo_grad: the minibatch is empty")
         lib = _lib.load()
         need = C.c_size_t()
-        _lib.check(lib.te_policy_grad_workspace_bytes_shaped(C.byref(self.shape), b, C.byref(need)), "te_policy_grad_workspace_bytes_shaped")
+        bf16 = self.grad_precision == "bf16"
+        if bf16:
+            _lib.check(lib.te_policy_grad_bf16_workspace_bytes(C.byref(self.shape), b, C.byref(need)), "te_policy_grad_bf16_workspace_bytes")
+        else:
+            _lib.check(lib.te_policy_grad_workspace_bytes_shaped(C.byref(self.shape), b, C.byref(need)), "te_policy_grad_workspace_bytes_shaped")
         ws = getattr(self, "_grad_ws", None)
         if ws is None or ws.numel() < need.value:
             if torch.cuda.is_current_stream_capturing():
@@ -340,6 +357,14 @@ class FusedPolicy:
             ws = self._grad_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
+            if bf16:
+                _lib.check(lib.te_policy_ppo_grad_bf16(self.params.data_ptr(), self.weights_bf16.data_ptr(), self.weights_bf16_t.data_ptr(),
+                                                       C.byref(self.shape), b, _ptr(index), lidar.data_ptr(), inertial.data_ptr(),
+                                                       last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(),
+                                                       ret.data_ptr(), _ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef),
+                                                       grad_out.data_ptr(), stats_out.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                           "te_policy_ppo_grad_bf16")
+                return
             _lib.check(lib.te_policy_ppo_grad_shaped(self.params.data_ptr(), C.byref(self.shape), b, _ptr(index), lidar.data_ptr(),
                                                      inertial.data_ptr(), last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(),
                                                      adv.data_ptr(), ret.data_ptr(), _ptr(adv_mean_std), float(clip), float(vf_coef),
@@ -355,7 +380,7 @@ class FusedPolicy:
                 require_f32("FusedPolicy", name, t, shape, self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            if self.weights_bf16 is not None:
+            if self.precision == "bf16":
                 _lib.check(_lib.load().te_policy_act_bf16(self.params.data_ptr(), self.weights_bf16.data_ptr(), C.byref(self.shape), n,
                                                           lidar.data_ptr(), inertial.data_ptr(), last_action.data_ptr(), _ptr(eps),
                                                           *(_ptr(o) for o in outs), stream), "te_policy_act_bf16")
@@ -510,7 +535,8 @@ class PPOConfig:
     # fused_forward through te_policy_act_bf16: weights and every layer's input rounded to bf16, the GEMMs on the bf16 MFMA with fp32
     # accumulation (FusedPolicy(precision="bf16"); the contract is in include/threatengage.h).  Needs fused_forward; applies to collect()
     # and to the bootstrap value, in both collect paths; update() is untouched.  What it costs: old_logp and the stored values come from
-    # the bf16 mean and value while update()'s forward is fp32, so the first epoch's ratio is not exactly 1.
+    # the bf16 mean and value while update()'s forward is fp32, so the first epoch's ratio is not exactly 1 (fused_update_bf16 below closes
+    # that gap: its forward is this one).
     # Measured on the MI355X (profiles/policy_bf16.json): at 65 536 rows the launch takes 0.246 ms for the default shape, 0.548 ms
     # for features_dim 512 with net_arch (128, 256, 512) and 0.549 ms with (512, 128, 256), against PyTorch's fp32 forward at 1.158 / 1.849 /
     # 2.049 ms, PyTorch under autocast(bfloat16) at 0.886 / 1.064 / 1.070 ms and the fp32 launch at 0.563 / 3.069 / 3.817 ms; collect() of
@@ -565,8 +591,24 @@ class PPOConfig:
     # (512, 128, 256), 2.1 x faster; at 65 536 rows 9.94 against 10.41 ms (1.05 x) and 11.78 against 10.25 ms: 0.87 x, SLOWER than autograd.
     # Off by default
     fused_update_wide: bool = False
+    # fused_update through te_policy_ppo_grad_bf16 (FusedPolicy(grad_precision="bf16")): forward, backward and weight gradients on the bf16
+    # MFMA with fp32 accumulation; the weights, every layer's input and every pre-activation gradient are rounded to bf16 once, the loss,
+    # log_std's gradient, the statistics, the partial sums and the gradient itself stay fp32 (the contract is in include/threatengage.h).
+    # Needs fused_update, and fused_update_wide for the wide shapes; independent of fused_forward_bf16; composes with fused_optimizer and
+    # fused_advantages.  Its forward is bitwise te_policy_act_bf16's, so with fused_forward_bf16 as well the first epoch's ratio is
+    # exactly 1 before any step.  What it costs: every tensor of the gradient is within 6 x 2^-8 of its largest per-row contribution of
+    # the contract evaluated in fp64 (tests/test_policy_grad_bf16.py), which is bf16's resolution, not fp32's.
+    # Measured on the MI355X (profiles/policy_grad_bf16.json), the call alone at 65 536 rows: 1.147 ms for the default shape, 2.688 ms
+    # for features_dim 512 with net_arch (128, 256, 512) and 3.072 ms with (512, 128, 256), against te_policy_ppo_grad_shaped's 2.730 / 9.525 /
+    # 11.515 ms in the same run (2.4 / 3.5 / 3.7 x; the spreads are below 1 %).  One minibatch (gradient + clip + Adam) at 65 536 rows: 1.57 /
+    # 3.12 / 3.50 ms against fast_learner's (autocast bf16) 6.36 / 7.75 / 7.52 ms and autograd fp32's 7.24 / 10.47 / 10.31 ms: the wide shapes
+    # no longer lose to fast_learner (2.5 x and 2.1 x faster).  At 8 192 rows 0.69 / 0.74 / 0.77 ms against fast_learner's 4.08 / 3.78 / 3.74 ms.
+    # Off by default
+    fused_update_bf16: bool = False
 
     def __post_init__(self):
+        if self.fused_update_bf16 and not self.fused_update:
+            raise ValueError("PPOConfig.fused_update_bf16 is fused_update's call with bf16 operands: it needs fused_update")
         if self.fused_optimizer and not self.fused_update:
             raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
         if self.fused_update_wide and not self.fused_update:
@@ -665,6 +707,8 @@ class PPO:
                                                            net_arch=self.cfg.net_arch)).to(self.device)
         if self.cfg.fused_update_wide and not self.cfg.fused_update:    # set after PPOConfig's own check
             raise ValueError("PPOConfig.fused_update_wide widens fused_update to every served shape: it needs fused_update")
+        if self.cfg.fused_update_bf16 and not self.cfg.fused_update:    # set after PPOConfig's own check
+            raise ValueError("PPOConfig.fused_update_bf16 is fused_update's call with bf16 operands: it needs fused_update")
         if (self.cfg.fused_update or self.cfg.fused_optimizer) and not is_default_shape(*policy_shape(self.policy)[1:]):
             if not self.cfg.fused_update_wide:
                 raise ValueError(GRAD_DEFAULT_ONLY)
@@ -717,8 +761,10 @@ class PPO:
             raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
         if self.cfg.fused_forward_bf16 and not self.cfg.fused_forward:      # set after PPOConfig's own check
             raise ValueError("PPOConfig.fused_forward_bf16 is fused_forward's launch with bf16 operands: it needs fused_forward")
-        self.fused = FusedPolicy(self.policy, precision="bf16" if self.cfg.fused_forward_bf16 else "fp32") if self.cfg.fused_forward else None
-        self.fused_grad = (self.fused or FusedPolicy(self.policy)) if self.cfg.fused_update else None
+        precisions = dict(precision="bf16" if self.cfg.fused_forward_bf16 else "fp32",
+                          grad_precision="bf16" if self.cfg.fused_update_bf16 else "fp32")     # one object serves both: the bf16 weights are shared
+        self.fused = FusedPolicy(self.policy, **precisions) if self.cfg.fused_forward else None
+        self.fused_grad = (self.fused or FusedPolicy(self.policy, **precisions)) if self.cfg.fused_update else None
         if self.cfg.fused_optimizer:    # the packed buffer becomes the single copy of the weights; the torch optimiser is dropped
             self.fused_grad.bind_parameters()
             self.opt = PackedAdam(self.fused_grad, lr=self.cfg.learning_rate, eps=1e-5)

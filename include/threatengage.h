@@ -521,6 +521,41 @@ int te_policy_act_bf16(const float* params, const uint16_t* weights_bf16, const 
                        const float* inertial, const float* last_action, const float* eps, float* mu, float* value, float* action,
                        float* logp, float* action_env, void* stream);
 
+/* te_policy_ppo_grad_bf16: te_policy_ppo_grad_shaped (below) with bf16 operands on v_mfma_f32_16x16x32_bf16 and fp32 accumulation, for
+ * every served shape and lidar_channels 2 and 3; opt-in, the fp32 calls are unchanged.  The loss, the arguments, grad (fp32, packed),
+ * stats [4] = pg, vl, ent, clip_frac, the rows read through `index`, no host synchronisation, no float atomics, fixed sum orders and
+ * graph capture are te_policy_ppo_grad_shaped's.  The numerics contract extends te_policy_act_bf16's:
+ *   1. forward: bitwise te_policy_act_bf16's on the same row and weights (weights rounded once; every layer input rounded to bf16
+ *      where it is stored; fp32 accumulation from the fp32 bias; mu and value fp32 fmaf sums over the bf16 last hidden tile).
+ *   2. saved activations: the workspace holds every layer's input as the bf16 values the MFMA consumed.  ReLU's mask is y > 0 on the
+ *      stored bf16 output y; tanh' is 1 - y^2 with that y, computed in fp32.
+ *   3. loss: the per-row loss and its derivatives are te_policy_ppo_grad's, in fp32 (the tie split of min, the closed clamp
+ *      interval, adv_mean_std).
+ *   4. dZ: every pre-activation gradient is computed in fp32 from the MFMA accumulator and rounded ONCE to bf16 (nearest-even) where
+ *      it is stored; the next dX, dW, db and the vector-ALU step from dmu / dv into the last hidden layer read the rounded value.
+ *      dmu and dv count as dZ.  The trunk's dZ is one accumulator over both heads.  log_std's per-row gradient and the four
+ *      statistics are not dZ of a GEMM: fp32 end to end.
+ *   5. dX = dZ W with the bf16 weights (weights_bf16_t); into the last hidden layer of a head with the fp32 mu / value weights.
+ *   6. dW = dZ^T [X | 1]: bf16 operands, fp32 accumulation, split-K slices of 2 048 reduction rows, fp32 partials summed slice by
+ *      slice in order.  The gradient is with respect to the fp32 master weights: the weight rounding is straight-through.
+ *   7. repeated calls are bitwise equal; `index` equals pre-gathered rows bitwise; rows past n contribute exactly 0, whatever the
+ *      workspace held.
+ * weights_bf16: te_policy_pack_bf16's buffer.  weights_bf16_t: a second uint16 buffer of te_policy_bf16_grad_words(shape) elements,
+ * 16-byte aligned, filled by te_policy_pack_bf16_grad from `params` in one launch (again after every change of `params`): per layer
+ * whose input needs a gradient (every layer of te_policy_pack_bf16's buffer except conv1, inertial.0 and action.0), in the same
+ * order, the transposed weight W^T [K][Np], Np = roundup(N, 32), columns N .. Np - 1 zero.
+ * workspace: 256-byte aligned, at least te_policy_grad_bf16_workspace_bytes(shape, n) bytes (about half the fp32 call's).  n <= 2^27.
+ * Null pointers, alignment (params, grad and both bf16 buffers 16 bytes; lidar and index 8; workspace 256; float arrays 4), a short
+ * workspace, clip_range and an unserved shape are refused before any launch, with te_last_error set. */
+int te_policy_bf16_grad_words(const te_policy_shape* shape, size_t* out_halfwords);
+int te_policy_pack_bf16_grad(const float* params, const te_policy_shape* shape, uint16_t* out, void* stream);
+int te_policy_grad_bf16_workspace_bytes(const te_policy_shape* shape, int32_t n, size_t* out_bytes);
+int te_policy_ppo_grad_bf16(const float* params, const uint16_t* weights_bf16, const uint16_t* weights_bf16_t, const te_policy_shape* shape,
+                            int32_t n, const int64_t* index, const float* lidar, const float* inertial, const float* last_action,
+                            const float* action, const float* old_logp, const float* adv, const float* ret, const float* adv_mean_std,
+                            float clip_range, float vf_coef, float ent_coef, float* grad, float* stats, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* The gradient of PPO's loss (dronechase_amd/ppo.py PPO.update) for one minibatch of n rows, in fp32:
  *   mu, v  = the policy of te_policy_act on row i;  sigma = exp(log_std)
  *   logp   = sum_j (-(action_j - mu_j)^2 / (2 sigma_j^2) - log_std_j - log(2 pi) / 2)
