@@ -1052,109 +1052,59 @@ static hipError_t set_lds_limits(const KernelPlan& k) {   // dynamic LDS beyond 
   return hipSuccess;
 }
 
-// The launch of one instance of a policy kernel template (ks[shape id][C - 2]: kernel(PolicyParams, args...)) on the shape's tile grid of n
-// rows.  A shape's LDS is above the 64 KB a launch gets by default: opt in once per (device, instance, in `opted`); not a stream operation, so a
-// capturing stream allows it.
-template <class... Args>
-using PolKernel = void (*)(PolicyParams, Args...);
+// The one launch of every policy kernel (the five tables below): kernel(args...) on ceil(rows / M) workgroups of the geometry the caller
+// read from the LDS plan that applies (pol_lds_plan for the fp32 tables, with kPolThreads; pol_lds_plan_bf16 / pol_grad_lds_plan_bf16 for
+// the bf16 ones).  A shape's LDS is above the 64 KB a launch gets by default: opt in once per (function, device), in the one `opted`
+// map; not a stream operation, so a capturing stream allows it.
+struct PolGeom { int M, threads, lds_bytes; };
+static PolGeom pol_geom(const PolLds& l) { return {l.M, kPolThreads, l.words * 4}; }
+template <class LdsB>
+static PolGeom pol_geom(const LdsB& l) { return {l.M, l.threads, l.bytes}; }
+
+static int policy_opt_in(const void* fn, int lds_bytes) {
+  static std::map<const void*, uint64_t> opted;
+  static std::mutex opted_lock;
+  int dev = 0;
+  TE_HIP(hipGetDevice(&dev));
+  std::lock_guard<std::mutex> hold(opted_lock);
+  uint64_t& bits = opted[fn];
+  if (dev < 64 && !(bits >> dev & 1)) {
+    TE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    bits |= 1ull << dev;
+  }
+  return 0;
+}
+
 template <class T>
 struct PolArg { using type = T; };   // the arguments convert to the kernel's formals; they do not deduce them
 
-template <int NS, class... Args>
-static int policy_launch(PolKernel<Args...> const (&ks)[NS][2], int shape_id, int32_t lidar_channels, const float* params, int n, void* stream,
-                         const typename PolArg<Args>::type&... args) {
-  static std::map<const void*, uint64_t> opted;
-  static std::mutex opted_lock;
-  const PolShape shape = pol_shape(shape_id, lidar_channels);
-  const PolLds lds = pol_lds_plan(shape);
-  const PolKernel<Args...> fn = ks[shape_id][lidar_channels - 2];
-  int dev = 0;
-  TE_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> hold(opted_lock);
-    uint64_t& bits = opted[reinterpret_cast<const void*>(fn)];
-    if (dev < 64 && !(bits >> dev & 1)) {
-      TE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds.words * 4));
-      bits |= 1ull << dev;
-    }
-  }
-  PolicyParams P = policy_layout(shape);
-  P.base = params;
-  const dim3 grid((unsigned)((n + lds.M - 1) / lds.M));
-  hipLaunchKernelGGL(fn, grid, dim3(kPolThreads), (size_t)lds.words * 4, (hipStream_t)stream, P, args...);
+template <class... Args>
+static int policy_launch(void (*fn)(Args...), PolGeom geom, int rows, void* stream, const typename PolArg<Args>::type&... args) {
+  if (policy_opt_in(reinterpret_cast<const void*>(fn), geom.lds_bytes)) return 1;
+  const dim3 grid((unsigned)((rows + geom.M - 1) / geom.M));
+  hipLaunchKernelGGL(fn, grid, dim3(geom.threads), (size_t)geom.lds_bytes, (hipStream_t)stream, args...);
   TE_HIP(hipGetLastError());
   return 0;
 }
 
-// every served instance of a policy kernel template K<C, shape id>
+// a caller's buffers bound to their layouts
+static PolicyParams policy_params(PolShape s, const float* params) { PolicyParams P = policy_layout(s); P.base = params; return P; }
+static PolicyBf16 policy_weights(PolShape s, const uint16_t* weights) { PolicyBf16 W = policy_bf16_layout(s); W.base = weights; return W; }
+static PolicyBf16 policy_weights_t(PolShape s, const uint16_t* weights_t) { PolicyBf16 W = policy_bf16_t_layout(s); W.base = weights_t; return W; }
+
+// every served instance of a policy kernel template K<C, shape id>: table[shape id][C - 2]
+template <class... Args>
+using PolKernel = void (*)(PolicyParams, Args...);
 #define TE_POL_INSTANCES(K) \
   {{&K<2, POL_SHAPE_DEFAULT>, &K<3, POL_SHAPE_DEFAULT>}, {&K<2, POL_SHAPE_BO>, &K<3, POL_SHAPE_BO>}, {&K<2, POL_SHAPE_LEARN>, &K<3, POL_SHAPE_LEARN>}}
 static_assert(POL_SHAPE_COUNT == 3, "TE_POL_INSTANCES lists every shape");
 static const PolKernel<PolicyIO> kPolicyActKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_act_kernel);
 static const PolKernel<PolicyIn, Params, int, float*> kPolicyDriveKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_drive_kernel);
 static const PolKernel<PolicyIn, GradTileArgs> kPolicyGradKernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_grad_tile_kernel);
-
-// te_policy_act_bf16's instances (te_policy_bf16.hpp) and their launch: policy_launch with the bf16 LDS plan and the second weight buffer
-using PolBf16Kernel = void (*)(PolicyParams, PolicyBf16, PolicyIO);
-static const PolBf16Kernel kPolicyActBf16Kernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_act_bf16_kernel);
-
-static int policy_launch_bf16(int shape_id, int32_t lidar_channels, const float* params, const uint16_t* weights, int n, void* stream,
-                              const PolicyIO& io) {
-  static std::map<const void*, uint64_t> opted;
-  static std::mutex opted_lock;
-  const PolShape shape = pol_shape(shape_id, lidar_channels);
-  const PolLdsB lds = pol_lds_plan_bf16(shape);
-  const PolBf16Kernel fn = kPolicyActBf16Kernels[shape_id][lidar_channels - 2];
-  int dev = 0;
-  TE_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> hold(opted_lock);
-    uint64_t& bits = opted[reinterpret_cast<const void*>(fn)];
-    if (dev < 64 && !(bits >> dev & 1)) {
-      TE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes));
-      bits |= 1ull << dev;
-    }
-  }
-  PolicyParams P = policy_layout(shape);
-  P.base = params;
-  PolicyBf16 W = policy_bf16_layout(shape);
-  W.base = weights;
-  const dim3 grid((unsigned)((n + lds.M - 1) / lds.M));
-  hipLaunchKernelGGL(fn, grid, dim3(lds.threads), (size_t)lds.bytes, (hipStream_t)stream, P, W, io);
-  TE_HIP(hipGetLastError());
-  return 0;
-}
-
-// te_policy_ppo_grad_bf16's tile kernel (te_policy_grad_bf16.hpp): its own LDS plan, both bf16 weight buffers
-using PolGradBf16Kernel = void (*)(PolicyParams, PolicyBf16, PolicyBf16, PolicyIn, GradTileArgsB);
-static const PolGradBf16Kernel kPolicyGradBf16Kernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_grad_bf16_tile_kernel);
-
-static int policy_launch_grad_bf16(int shape_id, int32_t lidar_channels, const float* params, const uint16_t* weights, const uint16_t* weights_t,
-                                   int rows, void* stream, const PolicyIn& in, const GradTileArgsB& t) {
-  static std::map<const void*, uint64_t> opted;
-  static std::mutex opted_lock;
-  const PolShape shape = pol_shape(shape_id, lidar_channels);
-  const PolGradLdsB lds = pol_grad_lds_plan_bf16(shape);
-  const PolGradBf16Kernel fn = kPolicyGradBf16Kernels[shape_id][lidar_channels - 2];
-  int dev = 0;
-  TE_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> hold(opted_lock);
-    uint64_t& bits = opted[reinterpret_cast<const void*>(fn)];
-    if (dev < 64 && !(bits >> dev & 1)) {
-      TE_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds.bytes));
-      bits |= 1ull << dev;
-    }
-  }
-  PolicyParams P = policy_layout(shape);
-  P.base = params;
-  PolicyBf16 W = policy_bf16_layout(shape), Wt = policy_bf16_t_layout(shape);
-  W.base = weights;
-  Wt.base = weights_t;
-  hipLaunchKernelGGL(fn, dim3((unsigned)(rows / lds.M)), dim3(lds.threads), (size_t)lds.bytes, (hipStream_t)stream, P, W, Wt, in, t);
-  TE_HIP(hipGetLastError());
-  return 0;
-}
+// te_policy_act_bf16's instances (te_policy_bf16.hpp) and te_policy_ppo_grad_bf16's tile kernel (te_policy_grad_bf16.hpp)
+static const PolKernel<PolicyBf16, PolicyIO> kPolicyActBf16Kernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_act_bf16_kernel);
+static const PolKernel<PolicyBf16, PolicyBf16, PolicyIn, GradTileArgsB> kPolicyGradBf16Kernels[POL_SHAPE_COUNT][2] =
+    TE_POL_INSTANCES(policy_grad_bf16_tile_kernel);
 
 static std::string shape_text(const PolShape& s) {
   std::string t = "features_dim " + std::to_string(s.F) + ", hidden";
@@ -1184,6 +1134,45 @@ static int policy_shape_id(const te_policy_shape* s, const char* fn) {
   std::string h;
   for (int i = 0; i < s->n_hidden; ++i) h += (i ? ", " : "") + std::to_string(s->hidden[i]);
   return fail(who + "hidden [" + h + "] is not served with features_dim " + std::to_string(s->features_dim) + served), -1;
+}
+
+// The element count of one of a served shape's buffers (layout: policy_layout, policy_bf16_layout or policy_bf16_t_layout)
+template <class Layout>
+static int policy_shaped_words(const char* fn, const te_policy_shape* shape, size_t* out, Layout layout) {
+  if (!out) return fail(std::string(fn) + ": null argument");
+  const int id = policy_shape_id(shape, fn);
+  if (id < 0) return 1;
+  *out = (size_t)layout(pol_shape(id, shape->lidar_channels)).words;
+  return 0;
+}
+
+// The bf16 copy of a served shape's weights: one thread per element of the plan (plan_of: policy_pack_plan or policy_pack_t_plan, with its kernel)
+template <class Plan, class Kernel>
+static int policy_pack(const char* fn, const float* params, const te_policy_shape* shape, uint16_t* out, void* stream, Plan (*plan_of)(PolShape),
+                       Kernel kernel) {
+  const std::string who = std::string(fn);
+  const int id = policy_shape_id(shape, fn);
+  if (id < 0) return 1;
+  if (!params || !out) return fail(who + ": null argument");
+  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if ((uintptr_t)out & 15) return fail(who + ": out must be 16-byte aligned");
+  const Plan plan = plan_of(pol_shape(id, shape->lidar_channels));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((plan.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, plan,
+                     reinterpret_cast<__bf16*>(out));
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+// The per-row inputs and the coefficients of PPO's loss, as the gradient entries get them, and their place in the tile kernel's arguments
+struct PolLossInputs {
+  const float *action, *old_logp, *adv, *ret, *adv_mean_std;
+  float clip_range, vf_coef, ent_coef;
+};
+
+template <class TileArgs>   // GradTileArgs or GradTileArgsB
+static void policy_loss_inputs(TileArgs& t, const PolLossInputs& in, int32_t n) {
+  t.action = in.action; t.old_logp = in.old_logp; t.adv = in.adv; t.ret = in.ret; t.adv_mean_std = in.adv_mean_std;
+  t.clip = in.clip_range; t.vf_coef = in.vf_coef; t.ent_coef = in.ent_coef; t.inv_n = 1.f / (float)n;
 }
 
 extern "C" {
@@ -1793,11 +1782,7 @@ __attribute__((visibility("default"))) int te_policy_shape_check(const te_policy
 }
 
 __attribute__((visibility("default"))) int te_policy_param_words_shaped(const te_policy_shape* shape, size_t* out_words) {
-  if (!out_words) return fail("te_policy_param_words_shaped: null argument");
-  const int id = policy_shape_id(shape, "te_policy_param_words_shaped");
-  if (id < 0) return 1;
-  *out_words = (size_t)policy_layout(pol_shape(id, shape->lidar_channels)).words;
-  return 0;
+  return policy_shaped_words("te_policy_param_words_shaped", shape, out_words, policy_layout);
 }
 
 __attribute__((visibility("default"))) int te_policy_param_words(int32_t lidar_channels, size_t* out_words) {
@@ -1805,21 +1790,36 @@ __attribute__((visibility("default"))) int te_policy_param_words(int32_t lidar_c
   return policy_words(lidar_channels, out_words);
 }
 
-// te_policy_act and te_policy_act_shaped behind their shape checks (fn: the caller's name in the messages)
-static int policy_act(const char* fn, int shape_id, const float* params, int32_t lidar_channels, int32_t n, const float* lidar,
-                      const float* inertial, const float* last_action, const float* eps, float* mu, float* value, float* action, float* logp,
-                      float* action_env, void* stream) {
+__attribute__((visibility("default"))) int te_policy_bf16_words(const te_policy_shape* shape, size_t* out_halfwords) {
+  return policy_shaped_words("te_policy_bf16_words", shape, out_halfwords, policy_bf16_layout);
+}
+
+__attribute__((visibility("default"))) int te_policy_pack_bf16(const float* params, const te_policy_shape* shape, uint16_t* out, void* stream) {
+  return policy_pack("te_policy_pack_bf16", params, shape, out, stream, policy_pack_plan, policy_pack_bf16_kernel);
+}
+
+// The three act entries behind their shape checks (fn: the caller's name in the messages).  bf16: te_policy_act_bf16, which also takes
+// weights_bf16 and launches the bf16 instance on its own LDS plan
+static int policy_act(const char* fn, bool bf16, int shape_id, const float* params, const uint16_t* weights_bf16, int32_t lidar_channels, int32_t n,
+                      const float* lidar, const float* inertial, const float* last_action, const float* eps, float* mu, float* value, float* action,
+                      float* logp, float* action_env, void* stream) {
   const std::string who = std::string(fn);
   if (n <= 0) return fail(who + ": n must be positive");
-  if (!params || !lidar || !inertial || !last_action || !mu || !value) return fail(who + ": null argument");
+  if (!params || (bf16 && !weights_bf16) || !lidar || !inertial || !last_action || !mu || !value) return fail(who + ": null argument");
   if (eps && (!action || !logp || !action_env)) return fail(who + ": eps given, so action, logp and action_env must be too");
   if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if (bf16 && ((uintptr_t)weights_bf16 & 15)) return fail(who + ": weights_bf16 must be 16-byte aligned");
   if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
   for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)eps, (const void*)mu, (const void*)value,
                         (const void*)action, (const void*)logp, (const void*)action_env})
     if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
   const PolicyIO io{lidar, inertial, last_action, eps, mu, value, eps ? action : nullptr, eps ? logp : nullptr, eps ? action_env : nullptr, n};
-  return policy_launch(kPolicyActKernels, shape_id, lidar_channels, params, n, stream, io);
+  const PolShape shape = pol_shape(shape_id, lidar_channels);
+  const PolicyParams P = policy_params(shape, params);
+  if (bf16)
+    return policy_launch(kPolicyActBf16Kernels[shape_id][lidar_channels - 2], pol_geom(pol_lds_plan_bf16(shape)), n, stream, P,
+                         policy_weights(shape, weights_bf16), io);
+  return policy_launch(kPolicyActKernels[shape_id][lidar_channels - 2], pol_geom(pol_lds_plan(shape)), n, stream, P, io);
 }
 
 __attribute__((visibility("default"))) int te_policy_act(const float* params, int32_t lidar_channels, int32_t n, const float* lidar,
@@ -1827,8 +1827,8 @@ __attribute__((visibility("default"))) int te_policy_act(const float* params, in
                                                          float* value, float* action, float* logp, float* action_env, void* stream) {
   size_t words;
   if (policy_words(lidar_channels, &words)) return 1;
-  return policy_act("te_policy_act", POL_SHAPE_DEFAULT, params, lidar_channels, n, lidar, inertial, last_action, eps, mu, value, action, logp,
-                    action_env, stream);
+  return policy_act("te_policy_act", false, POL_SHAPE_DEFAULT, params, nullptr, lidar_channels, n, lidar, inertial, last_action, eps, mu, value,
+                    action, logp, action_env, stream);
 }
 
 __attribute__((visibility("default"))) int te_policy_act_shaped(const float* params, const te_policy_shape* shape, int32_t n, const float* lidar,
@@ -1836,49 +1836,18 @@ __attribute__((visibility("default"))) int te_policy_act_shaped(const float* par
                                                                 float* value, float* action, float* logp, float* action_env, void* stream) {
   const int id = policy_shape_id(shape, "te_policy_act_shaped");
   if (id < 0) return 1;
-  return policy_act("te_policy_act_shaped", id, params, shape->lidar_channels, n, lidar, inertial, last_action, eps, mu, value, action, logp,
-                    action_env, stream);
-}
-
-__attribute__((visibility("default"))) int te_policy_bf16_words(const te_policy_shape* shape, size_t* out_halfwords) {
-  if (!out_halfwords) return fail("te_policy_bf16_words: null argument");
-  const int id = policy_shape_id(shape, "te_policy_bf16_words");
-  if (id < 0) return 1;
-  *out_halfwords = (size_t)policy_bf16_layout(pol_shape(id, shape->lidar_channels)).words;
-  return 0;
-}
-
-__attribute__((visibility("default"))) int te_policy_pack_bf16(const float* params, const te_policy_shape* shape, uint16_t* out, void* stream) {
-  const int id = policy_shape_id(shape, "te_policy_pack_bf16");
-  if (id < 0) return 1;
-  if (!params || !out) return fail("te_policy_pack_bf16: null argument");
-  if ((uintptr_t)params & 15) return fail("te_policy_pack_bf16: params must be 16-byte aligned");
-  if ((uintptr_t)out & 15) return fail("te_policy_pack_bf16: out must be 16-byte aligned");
-  const PolPackPlan plan = policy_pack_plan(pol_shape(id, shape->lidar_channels));
-  hipLaunchKernelGGL(policy_pack_bf16_kernel, dim3((unsigned)((plan.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, plan,
-                     reinterpret_cast<__bf16*>(out));
-  TE_HIP(hipGetLastError());
-  return 0;
+  return policy_act("te_policy_act_shaped", false, id, params, nullptr, shape->lidar_channels, n, lidar, inertial, last_action, eps, mu, value,
+                    action, logp, action_env, stream);
 }
 
 __attribute__((visibility("default"))) int te_policy_act_bf16(const float* params, const uint16_t* weights_bf16, const te_policy_shape* shape,
                                                               int32_t n, const float* lidar, const float* inertial, const float* last_action,
                                                               const float* eps, float* mu, float* value, float* action, float* logp,
                                                               float* action_env, void* stream) {
-  const std::string who = "te_policy_act_bf16";
   const int id = policy_shape_id(shape, "te_policy_act_bf16");
   if (id < 0) return 1;
-  if (n <= 0) return fail(who + ": n must be positive");
-  if (!params || !weights_bf16 || !lidar || !inertial || !last_action || !mu || !value) return fail(who + ": null argument");
-  if (eps && (!action || !logp || !action_env)) return fail(who + ": eps given, so action, logp and action_env must be too");
-  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
-  if ((uintptr_t)weights_bf16 & 15) return fail(who + ": weights_bf16 must be 16-byte aligned");
-  if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
-  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)eps, (const void*)mu, (const void*)value,
-                        (const void*)action, (const void*)logp, (const void*)action_env})
-    if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
-  const PolicyIO io{lidar, inertial, last_action, eps, mu, value, eps ? action : nullptr, eps ? logp : nullptr, eps ? action_env : nullptr, n};
-  return policy_launch_bf16(id, shape->lidar_channels, params, weights_bf16, n, stream, io);
+  return policy_act("te_policy_act_bf16", true, id, params, weights_bf16, shape->lidar_channels, n, lidar, inertial, last_action, eps, mu, value,
+                    action, logp, action_env, stream);
 }
 
 // te_drive_wingman and te_drive_wingman_shaped behind their shape checks
@@ -1897,7 +1866,9 @@ static int drive_wingman(const char* fn, int shape_id, te_env* e, int32_t wingma
   DeviceGuard guard(e->device);
   if (te_observe_wingman(e, wingman, lidar, inertial, last_action, nullptr, stream)) return 1;
   const PolicyIn in{lidar, inertial, last_action, nullptr, e->p.N};
-  return policy_launch(kPolicyDriveKernels, shape_id, lidar_channels, params, e->p.N, stream, in, e->p, (int)wingman, mu);
+  const PolShape shape = pol_shape(shape_id, lidar_channels);
+  return policy_launch(kPolicyDriveKernels[shape_id][lidar_channels - 2], pol_geom(pol_lds_plan(shape)), e->p.N, stream, policy_params(shape, params),
+                       in, e->p, (int)wingman, mu);
 }
 
 __attribute__((visibility("default"))) int te_drive_wingman(te_env* e, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar,
@@ -1915,50 +1886,65 @@ __attribute__((visibility("default"))) int te_drive_wingman_shaped(te_env* e, in
 }
 
 // The gradient entries behind their shape checks (fn: the caller's name in the messages; size_fn: the entry that tells the workspace's
-// size).  n up to 2^27: the conv1 layer's 12 * n reduction rows stay within int
+// size; bf16: te_policy_ppo_grad_bf16's workspace and kernels, te_policy_grad_bf16.hpp).  n up to 2^27: the conv1 layer's 12 * n
+// reduction rows stay within int
 static int policy_grad_rows_check(const std::string& who, int32_t n) {
   if (n <= 0) return fail(who + ": n must be positive");
   if (n > (1 << 27)) return fail(who + ": n must be at most 2^27");
   return 0;
 }
 
-static int policy_grad_workspace(const char* fn, int shape_id, int32_t lidar_channels, int32_t n, size_t* out_bytes) {
+static int policy_grad_workspace(const char* fn, bool bf16, int shape_id, int32_t lidar_channels, int32_t n, size_t* out_bytes) {
   if (policy_grad_rows_check(fn, n)) return 1;
   const PolShape shape = pol_shape(shape_id, lidar_channels);
-  *out_bytes = policy_grad_layout(shape, n, nullptr, policy_layout(shape), nullptr, nullptr, nullptr, nullptr);
+  *out_bytes = bf16 ? policy_grad_bf16_layout(shape, n, nullptr, policy_layout(shape), nullptr, nullptr, nullptr, nullptr)
+                    : policy_grad_layout(shape, n, nullptr, policy_layout(shape), nullptr, nullptr, nullptr, nullptr);
   return 0;
 }
 
-static int policy_ppo_grad(const char* fn, const char* size_fn, int shape_id, const float* params, int32_t lidar_channels, int32_t n,
-                           const int64_t* index, const float* lidar, const float* inertial, const float* last_action, const float* action,
-                           const float* old_logp, const float* adv, const float* ret, const float* adv_mean_std, float clip_range,
-                           float vf_coef, float ent_coef, float* grad, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
+static int policy_ppo_grad(const char* fn, const char* size_fn, bool bf16, int shape_id, const float* params, const uint16_t* weights_bf16,
+                           const uint16_t* weights_bf16_t, int32_t lidar_channels, int32_t n, const int64_t* index, const float* lidar,
+                           const float* inertial, const float* last_action, const PolLossInputs& loss, float* grad, float* stats, void* workspace,
+                           size_t workspace_bytes, void* stream) {
   const std::string who = std::string(fn);
   if (policy_grad_rows_check(who, n)) return 1;
-  if (!params || !lidar || !inertial || !last_action || !action || !old_logp || !adv || !ret || !grad || !stats || !workspace)
+  if (!params || (bf16 && (!weights_bf16 || !weights_bf16_t)) || !lidar || !inertial || !last_action || !loss.action || !loss.old_logp ||
+      !loss.adv || !loss.ret || !grad || !stats || !workspace)
     return fail(who + ": null argument");
   if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if (bf16 && ((uintptr_t)weights_bf16 & 15)) return fail(who + ": weights_bf16 must be 16-byte aligned");
+  if (bf16 && ((uintptr_t)weights_bf16_t & 15)) return fail(who + ": weights_bf16_t must be 16-byte aligned");
   if ((uintptr_t)grad & 15) return fail(who + ": grad must be 16-byte aligned");
   if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
   if ((uintptr_t)workspace & 255) return fail(who + ": workspace must be 256-byte aligned");
   if ((uintptr_t)index & 7) return fail(who + ": index must be 8-byte aligned");
-  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)action, (const void*)old_logp, (const void*)adv,
-                        (const void*)ret, (const void*)adv_mean_std, (const void*)stats})
+  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)loss.action, (const void*)loss.old_logp,
+                        (const void*)loss.adv, (const void*)loss.ret, (const void*)loss.adv_mean_std, (const void*)stats})
     if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
-  GradTileArgs t; GradPlan g;
+  GradTileArgs t; GradTileArgsB tb; GradPlan g;
   const PolShape shape = pol_shape(shape_id, lidar_channels);
-  const size_t need = policy_grad_layout(shape, n, static_cast<char*>(workspace), policy_layout(shape), grad, stats, &t, &g);
+  const PolicyParams P = policy_params(shape, params);
+  char* const ws = static_cast<char*>(workspace);
+  const size_t need = bf16 ? policy_grad_bf16_layout(shape, n, ws, P, grad, stats, &tb, &g) : policy_grad_layout(shape, n, ws, P, grad, stats, &t, &g);
   if (workspace_bytes < need)
     return fail(who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + size_fn + " says " + std::to_string(need) + ")");
-  if (!std::isfinite(clip_range) || clip_range < 0.f) return fail(who + ": clip_range must be finite and >= 0");
-  t.action = action; t.old_logp = old_logp; t.adv = adv; t.ret = ret; t.adv_mean_std = adv_mean_std;
-  t.clip = clip_range; t.vf_coef = vf_coef; t.ent_coef = ent_coef; t.inv_n = 1.f / (float)n;
+  if (!std::isfinite(loss.clip_range) || loss.clip_range < 0.f) return fail(who + ": clip_range must be finite and >= 0");
   const PolicyIn in{lidar, inertial, last_action, index, n};
   const hipStream_t s = (hipStream_t)stream;
-  // the tile grid covers the workspace's Bp rows (n rounded up to 32), not n: a 16-row shape's padding tile writes its rows too
+  // the tile grid covers the workspace's Bp rows (n rounded up to 32), not n: a 16-row shape's padding tile writes its rows too, and a
+  // padding row writes its zeros like any other
   const int Bp = g.L[POL_L_MU].R;
-  if (policy_launch(kPolicyGradKernels, shape_id, lidar_channels, params, Bp, stream, in, t)) return 1;
-  hipLaunchKernelGGL(policy_wgrad_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
+  if (bf16) {
+    policy_loss_inputs(tb, loss, n);
+    if (policy_launch(kPolicyGradBf16Kernels[shape_id][lidar_channels - 2], pol_geom(pol_grad_lds_plan_bf16(shape)), Bp, stream, P,
+                      policy_weights(shape, weights_bf16), policy_weights_t(shape, weights_bf16_t), in, tb))
+      return 1;
+  } else {
+    policy_loss_inputs(t, loss, n);
+    if (policy_launch(kPolicyGradKernels[shape_id][lidar_channels - 2], pol_geom(pol_lds_plan(shape)), Bp, stream, P, in, t)) return 1;
+  }
+  void (*const wgrad)(GradPlan) = bf16 ? policy_wgrad_bf16_kernel : policy_wgrad_kernel;
+  hipLaunchKernelGGL(wgrad, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
@@ -1969,14 +1955,19 @@ __attribute__((visibility("default"))) int te_policy_grad_workspace_bytes(int32_
   size_t words;
   if (!out_bytes) return fail("te_policy_grad_workspace_bytes: null argument");
   if (policy_words(lidar_channels, &words)) return 1;
-  return policy_grad_workspace("te_policy_grad_workspace_bytes", POL_SHAPE_DEFAULT, lidar_channels, n, out_bytes);
+  return policy_grad_workspace("te_policy_grad_workspace_bytes", false, POL_SHAPE_DEFAULT, lidar_channels, n, out_bytes);
+}
+
+// te_policy_grad_workspace_bytes_shaped (bf16 false) and te_policy_grad_bf16_workspace_bytes (true)
+static int policy_grad_workspace_shaped(const char* fn, bool bf16, const te_policy_shape* shape, int32_t n, size_t* out_bytes) {
+  if (!out_bytes) return fail(std::string(fn) + ": null argument");
+  const int id = policy_shape_id(shape, fn);
+  if (id < 0) return 1;
+  return policy_grad_workspace(fn, bf16, id, shape->lidar_channels, n, out_bytes);
 }
 
 __attribute__((visibility("default"))) int te_policy_grad_workspace_bytes_shaped(const te_policy_shape* shape, int32_t n, size_t* out_bytes) {
-  if (!out_bytes) return fail("te_policy_grad_workspace_bytes_shaped: null argument");
-  const int id = policy_shape_id(shape, "te_policy_grad_workspace_bytes_shaped");
-  if (id < 0) return 1;
-  return policy_grad_workspace("te_policy_grad_workspace_bytes_shaped", id, shape->lidar_channels, n, out_bytes);
+  return policy_grad_workspace_shaped("te_policy_grad_workspace_bytes_shaped", false, shape, n, out_bytes);
 }
 
 __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* params, int32_t lidar_channels, int32_t n, const int64_t* index,
@@ -1986,9 +1977,9 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad(const float* param
                                                               float* grad, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
   size_t words;
   if (policy_words(lidar_channels, &words)) return 1;
-  return policy_ppo_grad("te_policy_ppo_grad", "te_policy_grad_workspace_bytes", POL_SHAPE_DEFAULT, params, lidar_channels, n, index, lidar,
-                         inertial, last_action, action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef, grad, stats, workspace,
-                         workspace_bytes, stream);
+  return policy_ppo_grad("te_policy_ppo_grad", "te_policy_grad_workspace_bytes", false, POL_SHAPE_DEFAULT, params, nullptr, nullptr, lidar_channels,
+                         n, index, lidar, inertial, last_action, {action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef}, grad,
+                         stats, workspace, workspace_bytes, stream);
 }
 
 __attribute__((visibility("default"))) int te_policy_ppo_grad_shaped(const float* params, const te_policy_shape* shape, int32_t n,
@@ -1999,41 +1990,22 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad_shaped(const float
                                                                      void* workspace, size_t workspace_bytes, void* stream) {
   const int id = policy_shape_id(shape, "te_policy_ppo_grad_shaped");
   if (id < 0) return 1;
-  return policy_ppo_grad("te_policy_ppo_grad_shaped", "te_policy_grad_workspace_bytes_shaped", id, params, shape->lidar_channels, n, index,
-                         lidar, inertial, last_action, action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef, grad, stats,
-                         workspace, workspace_bytes, stream);
+  return policy_ppo_grad("te_policy_ppo_grad_shaped", "te_policy_grad_workspace_bytes_shaped", false, id, params, nullptr, nullptr,
+                         shape->lidar_channels, n, index, lidar, inertial, last_action,
+                         {action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef}, grad, stats, workspace, workspace_bytes, stream);
 }
 
 // ---- te_policy_ppo_grad_bf16 (te_policy_grad_bf16.hpp)
 __attribute__((visibility("default"))) int te_policy_bf16_grad_words(const te_policy_shape* shape, size_t* out_halfwords) {
-  if (!out_halfwords) return fail("te_policy_bf16_grad_words: null argument");
-  const int id = policy_shape_id(shape, "te_policy_bf16_grad_words");
-  if (id < 0) return 1;
-  *out_halfwords = (size_t)policy_bf16_t_layout(pol_shape(id, shape->lidar_channels)).words;
-  return 0;
+  return policy_shaped_words("te_policy_bf16_grad_words", shape, out_halfwords, policy_bf16_t_layout);
 }
 
 __attribute__((visibility("default"))) int te_policy_pack_bf16_grad(const float* params, const te_policy_shape* shape, uint16_t* out, void* stream) {
-  const int id = policy_shape_id(shape, "te_policy_pack_bf16_grad");
-  if (id < 0) return 1;
-  if (!params || !out) return fail("te_policy_pack_bf16_grad: null argument");
-  if ((uintptr_t)params & 15) return fail("te_policy_pack_bf16_grad: params must be 16-byte aligned");
-  if ((uintptr_t)out & 15) return fail("te_policy_pack_bf16_grad: out must be 16-byte aligned");
-  const PolPackTPlan plan = policy_pack_t_plan(pol_shape(id, shape->lidar_channels));
-  hipLaunchKernelGGL(policy_pack_bf16_t_kernel, dim3((unsigned)((plan.total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, plan,
-                     reinterpret_cast<__bf16*>(out));
-  TE_HIP(hipGetLastError());
-  return 0;
+  return policy_pack("te_policy_pack_bf16_grad", params, shape, out, stream, policy_pack_t_plan, policy_pack_bf16_t_kernel);
 }
 
 __attribute__((visibility("default"))) int te_policy_grad_bf16_workspace_bytes(const te_policy_shape* shape, int32_t n, size_t* out_bytes) {
-  if (!out_bytes) return fail("te_policy_grad_bf16_workspace_bytes: null argument");
-  const int id = policy_shape_id(shape, "te_policy_grad_bf16_workspace_bytes");
-  if (id < 0) return 1;
-  if (policy_grad_rows_check("te_policy_grad_bf16_workspace_bytes", n)) return 1;
-  const PolShape sh = pol_shape(id, shape->lidar_channels);
-  *out_bytes = policy_grad_bf16_layout(sh, n, nullptr, policy_layout(sh), nullptr, nullptr, nullptr, nullptr);
-  return 0;
+  return policy_grad_workspace_shaped("te_policy_grad_bf16_workspace_bytes", true, shape, n, out_bytes);
 }
 
 __attribute__((visibility("default"))) int te_policy_ppo_grad_bf16(const float* params, const uint16_t* weights_bf16, const uint16_t* weights_bf16_t,
@@ -2043,41 +2015,11 @@ __attribute__((visibility("default"))) int te_policy_ppo_grad_bf16(const float* 
                                                                    const float* adv_mean_std, float clip_range, float vf_coef, float ent_coef,
                                                                    float* grad, float* stats, void* workspace, size_t workspace_bytes,
                                                                    void* stream) {
-  const std::string who = "te_policy_ppo_grad_bf16";
   const int id = policy_shape_id(shape, "te_policy_ppo_grad_bf16");
   if (id < 0) return 1;
-  if (policy_grad_rows_check(who, n)) return 1;
-  if (!params || !weights_bf16 || !weights_bf16_t || !lidar || !inertial || !last_action || !action || !old_logp || !adv || !ret || !grad ||
-      !stats || !workspace)
-    return fail(who + ": null argument");
-  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
-  if ((uintptr_t)weights_bf16 & 15) return fail(who + ": weights_bf16 must be 16-byte aligned");
-  if ((uintptr_t)weights_bf16_t & 15) return fail(who + ": weights_bf16_t must be 16-byte aligned");
-  if ((uintptr_t)grad & 15) return fail(who + ": grad must be 16-byte aligned");
-  if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
-  if ((uintptr_t)workspace & 255) return fail(who + ": workspace must be 256-byte aligned");
-  if ((uintptr_t)index & 7) return fail(who + ": index must be 8-byte aligned");
-  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)action, (const void*)old_logp, (const void*)adv,
-                        (const void*)ret, (const void*)adv_mean_std, (const void*)stats})
-    if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
-  GradTileArgsB t; GradPlan g;
-  const PolShape sh = pol_shape(id, shape->lidar_channels);
-  const size_t need = policy_grad_bf16_layout(sh, n, static_cast<char*>(workspace), policy_layout(sh), grad, stats, &t, &g);
-  if (workspace_bytes < need)
-    return fail(who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_policy_grad_bf16_workspace_bytes says " +
-                std::to_string(need) + ")");
-  if (!std::isfinite(clip_range) || clip_range < 0.f) return fail(who + ": clip_range must be finite and >= 0");
-  t.action = action; t.old_logp = old_logp; t.adv = adv; t.ret = ret; t.adv_mean_std = adv_mean_std;
-  t.clip = clip_range; t.vf_coef = vf_coef; t.ent_coef = ent_coef; t.inv_n = 1.f / (float)n;
-  const PolicyIn in{lidar, inertial, last_action, index, n};
-  const hipStream_t s = (hipStream_t)stream;
-  // the tile grid covers the workspace's Bp rows (n rounded up to the tile): a padding row writes its zeros like any other
-  if (policy_launch_grad_bf16(id, shape->lidar_channels, params, weights_bf16, weights_bf16_t, t.Bp, stream, in, t)) return 1;
-  hipLaunchKernelGGL(policy_wgrad_bf16_kernel, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
-  TE_HIP(hipGetLastError());
-  hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
-  TE_HIP(hipGetLastError());
-  return 0;
+  return policy_ppo_grad("te_policy_ppo_grad_bf16", "te_policy_grad_bf16_workspace_bytes", true, id, params, weights_bf16, weights_bf16_t,
+                         shape->lidar_channels, n, index, lidar, inertial, last_action,
+                         {action, old_logp, adv, ret, adv_mean_std, clip_range, vf_coef, ent_coef}, grad, stats, workspace, workspace_bytes, stream);
 }
 
 // ---- optimiser step (te_policy_opt.hpp): every check is on the host, before any launch

@@ -302,6 +302,33 @@ __global__ __launch_bounds__(kPolThreads) void policy_grad_tile_kernel(PolicyPar
   }
 }
 
+// The split-K plan of shape S over Bp padded rows: layer l reduces dz[l] against x[l] (NULL where K = 0) into partials that take(bytes)
+// hands out in layer order, and policy_grad_combine_kernel sums them into grad (at P's offsets) and stats.  Host only; both workspace
+// layouts end in it.
+template <class Take>
+inline GradPlan policy_grad_plan(PolShape S, size_t Bp, const float* const (&dz)[kGradLayers], const float* const (&x)[kGradLayers], Take take,
+                                 float* grad, float* stats, const PolicyParams& P, int n) {
+  GradPlan g{};
+  for (int l = 0; l < kGradLayers; ++l) {
+    const PolLayer y = pol_layer(l, S);
+    GradLayer& L = g.L[l];
+    L.dz = dz[l];
+    L.x = x[l];
+    L.N = y.N; L.K = y.K; L.R = (int)(Bp * y.pos);
+    L.ntiles = (y.N + kGradTile - 1) / kGradTile;
+    L.ktiles = (y.K + 1 + kGradTile - 1) / kGradTile;
+    L.slices = (L.R + kGradSlice - 1) / kGradSlice;
+    L.wg0 = g.wgs; L.word0 = g.words;
+    g.wgs += L.slices * L.ntiles * L.ktiles;
+    g.words += y.N * (y.K + 1);
+    L.part = static_cast<float*>(take((size_t)L.slices * y.N * (y.K + 1) * sizeof(float)));
+    L.w_out = grad && l < POL_L_WEIGHTS ? grad + P.at[l].w : nullptr;
+    L.b_out = l == POL_L_STATS ? stats : (grad ? grad + (l == POL_L_LOGSTD ? P.log_std : P.at[l].b) : nullptr);
+    L.scale = l == POL_L_STATS ? 1.f / (float)n : 1.f;   // the statistics are means over the n rows
+  }
+  return g;
+}
+
 // The workspace of te_policy_ppo_grad for n rows (Bp = n rounded up to 32 for every shape: policy_wgrad_kernel stages 32 rows per step
 // and reads every one of them, so the tile kernel runs Bp / M tiles and a 16-row shape's padding tiles write their rows like any
 // padding row: zeros in dZ): every layer's input X [R][K] and pre-activation
@@ -311,34 +338,22 @@ inline size_t policy_grad_layout(PolShape S, int n, char* ws, const PolicyParams
   static_assert(kGradStep == kPolTileM && kGradSlice % kGradStep == 0, "Bp is a multiple of the split-K step, whatever the shape's tile");
   const size_t Bp = ((size_t)n + kGradStep - 1) / kGradStep * kGradStep;
   size_t off = 0;
-  auto take = [&](size_t rows, int cols) {
-    float* at = ws ? reinterpret_cast<float*>(ws + off) : nullptr;
-    off += (rows * cols * sizeof(float) + 255) / 256 * 256;
+  auto take = [&](size_t bytes) {
+    void* at = ws ? ws + off : nullptr;
+    off += (bytes + 255) / 256 * 256;
     return at;
   };
   GradTileArgs t{};
   for (int l = 0; l < POL_L_WEIGHTS; ++l) { const PolLayer y = pol_layer(l, S); t.save_pos[y.x] = y.pos; t.save_ld[y.x] = y.K; }
-  for (int sv = 0; sv < POL_SV_COUNT; ++sv) t.save[sv] = take(Bp * t.save_pos[sv], t.save_ld[sv]);
-  for (int l = 0; l < POL_L_COUNT; ++l) t.dz[l] = take(Bp * pol_layer(l, S).pos, pol_layer(l, S).N);
+  for (int sv = 0; sv < POL_SV_COUNT; ++sv) t.save[sv] = static_cast<float*>(take(Bp * t.save_pos[sv] * t.save_ld[sv] * sizeof(float)));
+  for (int l = 0; l < POL_L_COUNT; ++l) t.dz[l] = static_cast<float*>(take(Bp * pol_layer(l, S).pos * pol_layer(l, S).N * sizeof(float)));
 
-  GradPlan g{};
+  const float *dz[kGradLayers], *x[kGradLayers];
   for (int l = 0; l < kGradLayers; ++l) {
-    const PolLayer y = pol_layer(l, S);
-    GradLayer& L = g.L[l];
-    L.dz = t.dz[l];
-    L.x = l < POL_L_WEIGHTS ? t.save[y.x] : nullptr;
-    L.N = y.N; L.K = y.K; L.R = (int)(Bp * y.pos);
-    L.ntiles = (y.N + kGradTile - 1) / kGradTile;
-    L.ktiles = (y.K + 1 + kGradTile - 1) / kGradTile;
-    L.slices = (L.R + kGradSlice - 1) / kGradSlice;
-    L.wg0 = g.wgs; L.word0 = g.words;
-    g.wgs += L.slices * L.ntiles * L.ktiles;
-    g.words += y.N * (y.K + 1);
-    L.part = take((size_t)L.slices * y.N, y.K + 1);
-    L.w_out = grad && l < POL_L_WEIGHTS ? grad + P.at[l].w : nullptr;
-    L.b_out = l == POL_L_STATS ? stats : (grad ? grad + (l == POL_L_LOGSTD ? P.log_std : P.at[l].b) : nullptr);
-    L.scale = l == POL_L_STATS ? 1.f / (float)n : 1.f;   // the statistics are means over the n rows
+    dz[l] = t.dz[l];
+    x[l] = l < POL_L_WEIGHTS ? t.save[pol_layer(l, S).x] : nullptr;
   }
+  const GradPlan g = policy_grad_plan(S, Bp, dz, x, take, grad, stats, P, n);
   if (ta) *ta = t;
   if (gp) *gp = g;
   return off;

@@ -394,7 +394,7 @@ inline size_t policy_grad_bf16_layout(PolShape S, int n, char* ws, const PolicyP
   const size_t Bp = ((size_t)n + kPolGradBM - 1) / kPolGradBM * kPolGradBM;
   size_t off = 0;
   auto take = [&](size_t bytes) {
-    char* at = ws ? ws + off : nullptr;
+    void* at = ws ? ws + off : nullptr;
     off += (bytes + 255) / 256 * 256;
     return at;
   };
@@ -407,24 +407,12 @@ inline size_t policy_grad_bf16_layout(PolShape S, int n, char* ws, const PolicyP
   t.st = reinterpret_cast<float*>(take(Bp * 16));
   t.Bp = (int)Bp;
 
-  GradPlan g{};
+  const float *dz[kGradLayers], *x[kGradLayers];
   for (int l = 0; l < kGradLayers; ++l) {
-    const PolLayer y = pol_layer(l, S);
-    GradLayer& L = g.L[l];
-    L.dz = l < POL_L_WEIGHTS ? reinterpret_cast<const float*>(t.dz[l]) : (l == POL_L_LOGSTD ? t.dls : t.st);
-    L.x = l < POL_L_WEIGHTS ? reinterpret_cast<const float*>(t.save[y.x]) : nullptr;
-    L.N = y.N; L.K = y.K; L.R = (int)(Bp * y.pos);
-    L.ntiles = (y.N + kGradTile - 1) / kGradTile;
-    L.ktiles = (y.K + 1 + kGradTile - 1) / kGradTile;
-    L.slices = (L.R + kGradSlice - 1) / kGradSlice;
-    L.wg0 = g.wgs; L.word0 = g.words;
-    g.wgs += L.slices * L.ntiles * L.ktiles;
-    g.words += y.N * (y.K + 1);
-    L.part = reinterpret_cast<float*>(take((size_t)L.slices * y.N * (y.K + 1) * 4));
-    L.w_out = grad && l < POL_L_WEIGHTS ? grad + P.at[l].w : nullptr;
-    L.b_out = l == POL_L_STATS ? stats : (grad ? grad + (l == POL_L_LOGSTD ? P.log_std : P.at[l].b) : nullptr);
-    L.scale = l == POL_L_STATS ? 1.f / (float)n : 1.f;
+    dz[l] = l < POL_L_WEIGHTS ? reinterpret_cast<const float*>(t.dz[l]) : (l == POL_L_LOGSTD ? t.dls : t.st);
+    x[l] = l < POL_L_WEIGHTS ? reinterpret_cast<const float*>(t.save[pol_layer(l, S).x]) : nullptr;
   }
+  const GradPlan g = policy_grad_plan(S, Bp, dz, x, take, grad, stats, P, n);
   if (ta) *ta = t;
   if (gp) *gp = g;
   return off;

@@ -31,6 +31,8 @@ import os
 
 import pytest
 
+from tests._policy_cases import _gpu, _shape
+
 DEFAULT = (256, (64, 64))
 BO = (512, (128, 256, 512))
 LEARN = (512, (512, 128, 256))
@@ -53,12 +55,6 @@ def lib():
     from dronechase_amd.build import build_library
     build_library()
     return _lib.load()
-
-
-def _shape(c, features_dim, net_arch, n_hidden=None):
-    from dronechase_amd import _lib
-    h = list(net_arch)[:4] + [0] * (4 - min(4, len(net_arch)))
-    return _lib.PolicyShape(c, features_dim, len(net_arch) if n_hidden is None else n_hidden, (C.c_int32 * 4)(*h))
 
 
 def _q(x):
@@ -218,13 +214,6 @@ def test_the_reference_pair_agrees(lib):
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return torch
-
-
 def _to_gpu(obs):
     return {k: v.to("cuda:0").contiguous() for k, v in obs.items()}
 

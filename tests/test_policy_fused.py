@@ -12,6 +12,8 @@ import re
 import numpy as np
 import pytest
 
+from tests._policy_cases import _gpu, _obs, _policy, _trained_policy
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ATOL = RTOL = 1e-4
 
@@ -90,42 +92,6 @@ def test_bad_arguments_fail_through_last_error(lib):
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return torch
-
-
-def _obs(torch, n, c, seed):
-    g = torch.Generator(device="cuda:0").manual_seed(seed)
-    u = lambda *s: torch.rand(*s, generator=g, device="cuda:0")
-    return {"lidar": u(n, c, 13, 26), "inertial_data": u(n, 15) * 2 - 1, "last_action": u(n, 4) * 2 - 1}
-
-
-def _policy(torch, c, seed):
-    from dronechase_amd.ppo import LidarInertialActionPolicy
-    torch.manual_seed(seed)
-    p = LidarInertialActionPolicy(lidar_shape=(c, 13, 26)).to("cuda:0")
-    with torch.no_grad():
-        p.log_std.copy_(torch.tensor([0.2, -0.3, 0.1, -0.5]))
-    return p
-
-
-def _trained_policy(torch, c):
-    """Weights after a short PPO run on the real environment, and the observations of that run's last rollout."""
-    from dronechase_amd import default_config
-    from dronechase_amd.batched_env import BatchedEnv
-    from dronechase_amd.ppo import PPO, PPOConfig
-    env = BatchedEnv(default_config("stage03", n_envs=512, max_step=40, lidar_channels=c), "cuda:0")
-    ppo = PPO(env, PPOConfig(n_steps=8, batch_size=1024, n_epochs=2), seed=2)
-    ppo.collect(); ppo.update(); ppo.collect()
-    obs = {k: v.reshape(-1, *v.shape[2:]).clone() for k, v in ppo.buf.obs.items()}   # 8 x 512 = 4 096 real te_step observations
-    policy = ppo.policy
-    env.close()
-    return policy, obs
-
-
 MARGIN = {"mu": [0.0, 0.0], "value": [0.0, 0.0]}     # largest |d|, largest |d| / (ATOL + RTOL |ref|)
 
 
@@ -142,7 +108,7 @@ def _check(torch, got, ref, name):
 def test_parity_with_the_module(c):
     torch = _gpu()
     from dronechase_amd.ppo import FusedPolicy
-    trained, real = _trained_policy(torch, c)
+    trained, real = _trained_policy(torch, c, n_envs=512, batch_size=1024)      # 8 x 512 = 4 096 real te_step observations
     for label, policy in (("random", _policy(torch, c, 5)), ("trained", trained)):
         fused = FusedPolicy(policy)
         sources = [("random", n, _obs(torch, n, c, n)) for n in (1, 63, 64, 65, 4097, 65536)]

@@ -25,6 +25,7 @@ import os
 import pytest
 
 from _kinkfree import CLIP, ENT_COEF, SHAPES, VF_COEF, packed_names
+from _policy_cases import _gpu, _shape
 
 DEFAULT, BO, LEARN = SHAPES["default"], SHAPES["BO"], SHAPES["learn"]
 INSTANCES = [(name, c) for name in SHAPES for c in (2, 3)]
@@ -42,12 +43,6 @@ def lib():
 def _ref():
     import _policy_grad_bf16_ref as R
     return R
-
-
-def _shape(c, features_dim, net_arch, n_hidden=None):
-    from dronechase_amd import _lib
-    h = list(net_arch)[:4] + [0] * (4 - min(4, len(net_arch)))
-    return _lib.PolicyShape(c, features_dim, len(net_arch) if n_hidden is None else n_hidden, (C.c_int32 * 4)(*h))
 
 
 def _record(rec):
@@ -197,13 +192,6 @@ def test_ppo_refuses_the_switch_set_after_the_config_check(lib):
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return torch
-
-
 def _dev(d):
     return {k: v.to("cuda:0").contiguous() for k, v in d.items()}
 

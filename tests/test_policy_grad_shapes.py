@@ -16,10 +16,11 @@ import re
 import numpy as np
 import pytest
 
+from tests._policy_cases import DEFAULT, _compare, _gpu, _kernel, _obs, _policy, _ref, _rollout, _shape, _trained_policy
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REL, ABS, KINK = 1e-4, 1e-6, 0.02
 
-DEFAULT = (256, (64, 64))
 BO = (512, (128, 256, 512))
 LEARN = (512, (512, 128, 256))
 WIDE = {"reference BO": BO, "reference learn": LEARN}
@@ -32,12 +33,6 @@ def lib():
     from dronechase_amd.build import build_library
     build_library()
     return _lib.load()
-
-
-def _shape(c, features_dim, net_arch, n_hidden=None):
-    from dronechase_amd import _lib
-    h = list(net_arch)[:4] + [0] * (4 - min(4, len(net_arch)))
-    return _lib.PolicyShape(c, features_dim, len(net_arch) if n_hidden is None else n_hidden, (C.c_int32 * 4)(*h))
 
 
 def _ws_bytes(lib, c, shape, n):
@@ -161,121 +156,7 @@ def test_config_switch(lib):
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return torch
-
-
-def _policy(torch, c, seed, shape):
-    from dronechase_amd.ppo import LidarInertialActionPolicy
-    torch.manual_seed(seed)
-    p = LidarInertialActionPolicy(lidar_shape=(c, 13, 26), features_dim=shape[0], net_arch=shape[1]).to("cuda:0")
-    with torch.no_grad():
-        p.log_std.copy_(torch.tensor([0.2, -0.3, 0.1, -0.5]))
-    return p
-
-
-def _obs(torch, n, c, seed):
-    g = torch.Generator(device="cuda:0").manual_seed(seed)
-    u = lambda *s: torch.rand(*s, generator=g, device="cuda:0")
-    return {"lidar": u(n, c, 13, 26), "inertial_data": u(n, 15) * 2 - 1, "last_action": u(n, 4) * 2 - 1}
-
-
-def _rollout(torch, policy, obs, seed, shift=0.3):
-    """action, old_logp, adv, ret for the rows of obs: actions drawn from the policy, old_logp its log-prob shifted by
-    N(0, shift) so that both branches of the clip are taken."""
-    g = torch.Generator(device="cuda:0").manual_seed(seed)
-    n = obs["lidar"].shape[0]
-    r = lambda *s: torch.randn(*s, generator=g, device="cuda:0")
-    with torch.no_grad():
-        d, v = policy.dist(obs)
-        action = d.mean + d.stddev * r(n, 4)
-        old_logp = d.log_prob(action).sum(-1) + shift * r(n)
-    return {"action": action.contiguous(), "old_logp": old_logp.contiguous(), "adv": (r(n) * 2 + 0.3).contiguous(),
-            "ret": (v + r(n)).contiguous()}
-
-
-def _trained_policy(torch, c, shape):
-    """Weights after a short autograd PPO run on the real environment, and the 8 x 64 observations of that run's last rollout."""
-    from dronechase_amd import default_config
-    from dronechase_amd.batched_env import BatchedEnv
-    from dronechase_amd.ppo import PPO, PPOConfig
-    env = BatchedEnv(default_config("stage03", n_envs=64, max_step=40, lidar_channels=c), "cuda:0")
-    ppo = PPO(env, PPOConfig(n_steps=8, batch_size=256, n_epochs=2, features_dim=shape[0], net_arch=shape[1]), seed=2)
-    ppo.collect(); ppo.update(); ppo.collect()
-    obs = {k: v.reshape(-1, *v.shape[2:]).clone() for k, v in ppo.buf.obs.items()}
-    policy = ppo.policy
-    env.close()
-    return policy, obs
-
-
-def _ref(torch, policy, obs, ro, index, norm, clip, vf, ent, dtype=None):
-    """Autograd through the module (fp32; or a copy in `dtype`): (packed gradient, [pg, vl, ent, clip_frac], the [mean, std]
-    the kernel gets)."""
-    import copy
-    from dronechase_amd.ppo import _packed_order
-    if dtype is not None:
-        policy = copy.deepcopy(policy).to(dtype)
-        obs = {k: v.to(dtype) for k, v in obs.items()}
-        ro = {k: v.to(dtype) for k, v in ro.items()}
-    sel = (lambda t: t) if index is None else (lambda t: t[index])
-    params = _packed_order(policy)
-    mu, v = policy({k: sel(o) for k, o in obs.items()})
-    d = torch.distributions.Normal(mu, policy.log_std.exp().expand_as(mu), validate_args=False)
-    logp = d.log_prob(sel(ro["action"])).sum(-1)
-    a = sel(ro["adv"])
-    ms = torch.stack((a.mean(), a.std())) if norm else None
-    if norm:
-        a = (a - a.mean()) / (a.std() + 1e-8)
-    ratio = (logp - sel(ro["old_logp"])).exp()
-    pg = -torch.min(a * ratio, a * ratio.clamp(1 - clip, 1 + clip)).mean()
-    vl = torch.nn.functional.mse_loss(v, sel(ro["ret"]))
-    e = d.entropy().sum(-1).mean()
-    loss = pg + vf * vl - ent * e
-    grads = torch.autograd.grad(loss, params)
-    stats = torch.stack((pg, vl, e, ((ratio - 1).abs() > clip).float().mean())).detach()
-    return torch.cat([g.reshape(-1) for g in grads]).float(), stats.float(), (ms.detach().float().contiguous() if norm else None)
-
-
-def _kernel(torch, fused, obs, ro, index, ms, clip, vf, ent):
-    grad = torch.full_like(fused.params, float("nan"))
-    stats = torch.full((4,), float("nan"), device="cuda:0")
-    fused.ppo_grad(obs, index, ro["action"], ro["old_logp"], ro["adv"], ro["ret"], ms, clip, vf, ent, grad, stats)
-    torch.cuda.synchronize()
-    return grad, stats
-
-
 GAP = {"grad": 0.0, "stats": 0.0}      # largest |d| / bound seen
-
-
-def _compare(torch, policy, grad, ref, stats, ref_stats, label, rows, ref64):
-    """Every packed tensor within REL ||g||_inf + ABS + KINK / B of the fp32 reference; the gaps of all tensors that are not are
-    reported together, with the fp64 module's view of them (ref64(): computed only then)."""
-    from dronechase_amd.ppo import _packed_order
-    names = [n for n, _ in policy.named_parameters() if n != "log_std"] + ["log_std"]
-    off, bad, r64 = 0, [], None
-    assert bool(torch.isfinite(grad).all()) and bool(torch.isfinite(stats).all()), label
-    for name, p in zip(names, _packed_order(policy)):
-        sl = slice(off, off + p.numel())
-        g, r = grad[sl], ref[sl]
-        off += p.numel()
-        d, bound = float((g - r).abs().max()), REL * float(r.abs().max()) + ABS + KINK / rows
-        GAP["grad"] = max(GAP["grad"], d / bound)
-        if d > bound:
-            r64 = ref64() if r64 is None else r64
-            bad.append(f"{name}: |d| {d:.3e} > {bound:.3e} (||g|| {float(r.abs().max()):.3e}); vs fp64: kernel "
-                       f"{float((g - r64[sl]).abs().max()):.3e}, fp32 autograd {float((r - r64[sl]).abs().max()):.3e}")
-    assert off == grad.numel()
-    ds = (stats - ref_stats).abs()
-    sb = REL * ref_stats.abs() + ABS
-    GAP["stats"] = max(GAP["stats"], float((ds / sb).max()))
-    if not bool((ds <= sb).all()):
-        bad.append(f"stats {stats.tolist()} vs {ref_stats.tolist()}")
-    if bad:
-        print(f"\n{label}:\n  " + "\n  ".join(bad))
-    assert not bad, f"{label}: {bad}"
 
 
 @pytest.mark.gpu
@@ -292,7 +173,7 @@ def test_gradient_parity_with_autograd(name, c):
         cases.append((random, f"random B={n}", obs, _rollout(torch, random, obs, n), None, norm, ent))
     obs = _obs(torch, 3000, c, 7)
     cases.append((random, "random rows, index B=1000", obs, _rollout(torch, random, obs, 7), torch.randperm(3000, device="cuda:0")[:1000], True, 0.01))
-    trained, real = _trained_policy(torch, c, shape)
+    trained, real = _trained_policy(torch, c, n_envs=64, batch_size=256, shape=shape)
     cases.append((trained, "trained weights, te_step B=512", real, _rollout(torch, trained, real, 99), None, True, 0.0))
     fused = {id(random): FusedPolicy(random), id(trained): FusedPolicy(trained)}
     for policy, src, obs, ro, idx, norm, ent in cases:
@@ -300,7 +181,8 @@ def test_gradient_parity_with_autograd(name, c):
         grad, stats = _kernel(torch, fused[id(policy)], obs, ro, idx, ms, 0.2, 0.5, ent)
         tag = f"{name} C={c}, {src}"
         ref64 = lambda: _ref(torch, policy, obs, ro, idx, norm, 0.2, 0.5, ent, dtype=torch.float64)[0]
-        _compare(torch, policy, grad, ref, stats, ref_stats, tag, obs["lidar"].shape[0] if idx is None else idx.numel(), ref64)
+        _compare(torch, policy, grad, ref, stats, ref_stats, tag, obs["lidar"].shape[0] if idx is None else idx.numel(), ref64,
+                 tol=(REL, ABS, KINK), gap=GAP)
         if obs["lidar"].shape[0] == 2081:      # both clip branches were taken
             assert 0.1 < float(stats[3]) < 0.9, (tag, stats.tolist())
     print(f"\n{name} C={c}: largest |d| as a fraction of the bound so far: gradient {GAP['grad']:.3f}, statistics {GAP['stats']:.3f}")

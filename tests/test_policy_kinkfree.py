@@ -45,6 +45,7 @@ import os
 import pytest
 
 from tests import _kinkfree as K
+from tests._policy_cases import _gpu
 
 CASES = {3: [(1, None), (16, None), (17, None), (32, None), (33, None), (33, 80), (2081, None)], 2: [(17, None), (33, None)]}
 INSTANCES = [(name, c) for name in K.SHAPES for c in (3, 2)]
@@ -148,13 +149,6 @@ def test_the_bound_bites_where_the_old_one_does_not():
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return torch
-
-
 def _record(rec):
     print("\n" + json.dumps(rec))
     if os.environ.get("TE_POLICY_KINKFREE_RECORD"):

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 from tests._adam_ref import ref64_step
+from tests._policy_cases import _gpu, _obs, _policy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SLICE = 4096                     # kOptSlice: the words one workgroup owns
@@ -106,13 +107,6 @@ def test_fused_optimizer_needs_fused_update():
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return torch
-
-
 def _zero_block(words):
     return slice(words // 5, 2 * words // 5)      # never-read cells: exact zeros in every gradient (empty for words == 1)
 
@@ -265,21 +259,6 @@ def test_graph_replay_advances_the_step(lib):
     torch.cuda.synchronize()
     assert int(state[0:1].view(torch.int32)) == 3
     assert torch.equal(p, eager_p) and torch.equal(state.view(torch.int32), eager_s.view(torch.int32))
-
-
-def _policy(torch, c, seed):
-    from dronechase_amd.ppo import LidarInertialActionPolicy
-    torch.manual_seed(seed)
-    p = LidarInertialActionPolicy(lidar_shape=(c, 13, 26)).to("cuda:0")
-    with torch.no_grad():
-        p.log_std.copy_(torch.tensor([0.2, -0.3, 0.1, -0.5]))
-    return p
-
-
-def _obs(torch, n, c, seed):
-    g = torch.Generator(device="cuda:0").manual_seed(seed)
-    u = lambda *s: torch.rand(*s, generator=g, device="cuda:0")
-    return {"lidar": u(n, c, 13, 26), "inertial_data": u(n, 15) * 2 - 1, "last_action": u(n, 4) * 2 - 1}
 
 
 def _grad_like(torch, params, seed):

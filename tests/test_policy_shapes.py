@@ -13,10 +13,11 @@ import re
 import numpy as np
 import pytest
 
+from tests._policy_cases import DEFAULT, _gpu, _obs, _policy, _shape, _trained_policy
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ATOL = RTOL = 1e-4
 
-DEFAULT = (256, (64, 64))
 BO = (512, (128, 256, 512))
 LEARN = (512, (512, 128, 256))
 SERVED = {"default": DEFAULT, "reference BO": BO, "reference learn": LEARN}
@@ -38,12 +39,6 @@ def lib():
     from dronechase_amd.build import build_library
     build_library()
     return _lib.load()
-
-
-def _shape(c, features_dim, net_arch, n_hidden=None):
-    from dronechase_amd import _lib
-    h = list(net_arch)[:4] + [0] * (4 - min(4, len(net_arch)))
-    return _lib.PolicyShape(c, features_dim, len(net_arch) if n_hidden is None else n_hidden, (C.c_int32 * 4)(*h))
 
 
 # ---------------------------------------------------------------------------------------------------------- no GPU needed
@@ -231,42 +226,6 @@ def test_fused_update_refuses_other_shapes(lib):
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X
-def _gpu():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.fail("no GPU visible: -m gpu tests must run on the MI355X box")
-    return torch
-
-
-def _obs(torch, n, c, seed):
-    g = torch.Generator(device="cuda:0").manual_seed(seed)
-    u = lambda *s: torch.rand(*s, generator=g, device="cuda:0")
-    return {"lidar": u(n, c, 13, 26), "inertial_data": u(n, 15) * 2 - 1, "last_action": u(n, 4) * 2 - 1}
-
-
-def _policy(torch, c, seed, shape=BO):
-    from dronechase_amd.ppo import LidarInertialActionPolicy
-    torch.manual_seed(seed)
-    p = LidarInertialActionPolicy(lidar_shape=(c, 13, 26), features_dim=shape[0], net_arch=shape[1]).to("cuda:0")
-    with torch.no_grad():
-        p.log_std.copy_(torch.tensor([0.2, -0.3, 0.1, -0.5]))
-    return p
-
-
-def _trained_policy(torch, c, shape):
-    """Weights after a short PPO run (autograd update) on the real environment, and the observations of that run's last rollout."""
-    from dronechase_amd import default_config
-    from dronechase_amd.batched_env import BatchedEnv
-    from dronechase_amd.ppo import PPO, PPOConfig
-    env = BatchedEnv(default_config("stage03", n_envs=512, max_step=40, lidar_channels=c), "cuda:0")
-    ppo = PPO(env, PPOConfig(n_steps=8, batch_size=1024, n_epochs=2, features_dim=shape[0], net_arch=shape[1]), seed=2)
-    ppo.collect(); ppo.update(); ppo.collect()
-    obs = {k: v.reshape(-1, *v.shape[2:]).clone() for k, v in ppo.buf.obs.items()}   # 8 x 512 = 4 096 real te_step observations
-    policy = ppo.policy
-    env.close()
-    return policy, obs
-
-
 MARGIN = {"mu": [0.0, 0.0], "value": [0.0, 0.0]}     # largest |d|, largest |d| / (ATOL + RTOL |ref|)
 
 
@@ -284,7 +243,7 @@ def _check(torch, got, ref, name):
 def test_parity_with_the_module(shape, c):
     torch = _gpu()
     from dronechase_amd.ppo import FusedPolicy
-    trained, real = _trained_policy(torch, c, shape)
+    trained, real = _trained_policy(torch, c, n_envs=512, batch_size=1024, shape=shape)      # 8 x 512 = 4 096 real te_step observations
     M = TILE_ROWS[shape]
     for label, policy in (("random", _policy(torch, c, 5, shape)), ("trained", trained)):
         fused = FusedPolicy(policy)
@@ -329,7 +288,7 @@ def test_shaped_entry_with_the_default_shape_is_te_policy_act(lib, c):
 def test_rows_are_independent_and_calls_deterministic():
     torch = _gpu()
     from dronechase_amd.ppo import FusedPolicy
-    fused = FusedPolicy(_policy(torch, 3, 9))
+    fused = FusedPolicy(_policy(torch, 3, 9, BO))
     n = 4097
     obs = _obs(torch, n, 3, 3)
     eps = torch.randn(n, 4, device="cuda:0")
@@ -347,7 +306,7 @@ def test_rows_are_independent_and_calls_deterministic():
 def test_sampling_matches_the_hand_formula():
     torch = _gpu()
     from dronechase_amd.ppo import FusedPolicy
-    p = _policy(torch, 3, 7)
+    p = _policy(torch, 3, 7, BO)
     fused = FusedPolicy(p)
     obs = _obs(torch, 4097, 3, 1)
     eps = torch.randn(4097, 4, device="cuda:0") * 2
@@ -381,7 +340,7 @@ def test_drive_shaped_matches_the_four_call_sequence_bitwise():
     cfg = default_config("exp05", n_envs=n, motor_noise=1, seed=17, max_step=14)
     A, B = BatchedEnv(cfg, "cuda:0"), BatchedEnv(cfg, "cuda:0")
     A.reset(); B.reset()
-    policy = _policy(torch, 3, 5)
+    policy = _policy(torch, 3, 5, BO)
     with torch.no_grad():       # a mean that leaves [-1, 1] in a share of the rows, so the clamp matters
         policy.mu.weight.mul_(8.0)
         policy.mu.bias.copy_(torch.tensor([1.2, -1.2, 0.2, 0.3]))
