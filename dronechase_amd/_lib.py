@@ -19,7 +19,7 @@ EXPORTS = (
     "te_profile_end", "te_debug_stamps", "te_abi_version", "te_last_error", "te_step_stacked", "te_observe_stacked", "te_observe_ally", "te_set_ally_actions", "te_wingman_info", "te_calculate_rounds", "te_observe_wingman", "te_set_wingman_actions", "te_drive_wingman", "te_quad_preset", "te_step_students", "te_set_persistent_obs",
     "te_policy_shape_check", "te_policy_param_words_shaped", "te_policy_act_shaped", "te_drive_wingman_shaped",
     "te_policy_grad_workspace_bytes_shaped", "te_policy_ppo_grad_shaped",
-    "te_policy_bf16_words", "te_policy_pack_bf16", "te_policy_act_bf16",
+    "te_policy_bf16_words", "te_policy_pack_bf16", "te_policy_act_bf16", "te_drive_wingman_bf16",
     "te_policy_bf16_grad_words", "te_policy_pack_bf16_grad", "te_policy_grad_bf16_workspace_bytes", "te_policy_ppo_grad_bf16",
     "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad", "te_kernel_plan",
     "te_policy_opt_state_bytes", "te_policy_adam_step",
@@ -96,6 +96,7 @@ def load() -> C.CDLL:
     L.te_policy_pack_bf16.argtypes = [vp, shape, vp, vp]
     L.te_policy_act_bf16.argtypes = [vp, vp, shape, i32] + [vp] * 9 + [vp]
     L.te_drive_wingman_shaped.argtypes = [vp, i32, vp, shape] + [vp] * 4 + [vp]
+    L.te_drive_wingman_bf16.argtypes = [vp, i32, vp, vp, shape] + [vp] * 4 + [vp]
     L.te_policy_grad_workspace_bytes.argtypes = [i32, i32, C.POINTER(C.c_size_t)]
     f32 = C.c_float
     L.te_policy_ppo_grad.argtypes = [vp, i32, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]

@@ -182,13 +182,20 @@ class BatchedEnv:
     def drive_wingman(self, wingman: int, fused_policy, mu: Optional[torch.Tensor] = None) -> None:
         """drive_lw_rl_agent for a caller-driven pursuer in one te_drive_wingman call: its observation, the deterministic action of
         `fused_policy` (a ppo.FusedPolicy: its packed buffer is read at launch time) and the drive of every env whose pursuer is
-        armed.  mu [N, 4] f32 (optional) receives the unclamped mean of every row.  No allocation after the first call and no host
+        armed.  mu [N, 4] f32 (optional) receives the unclamped mean of every row.  The forward follows the policy's `precision`:
+        "fp32" goes to te_drive_wingman_shaped, "bf16" to te_drive_wingman_bf16 with the policy's weights_bf16 (the mean is then
+        bitwise fused_policy.forward's on the same rows, as for fp32).  No allocation after the first call and no host
         synchronisation: a HIP graph can capture it."""
         lidar, inertial, last_action = self.wingman_scratch(wingman)
         if fused_policy.device != self.device:
             raise ValueError(f"drive_wingman: the policy lives on {fused_policy.device}, the env on {self.device}")
         if mu is not None:
             require_f32("drive_wingman", "mu", mu, (self.N, 4), self.device, shown=f"[{self.N}, 4]")
+        if fused_policy.precision == "bf16":
+            _lib.check(self.L.te_drive_wingman_bf16(self._h, int(wingman), self._p(fused_policy.params), self._p(fused_policy.weights_bf16),
+                                                    C.byref(fused_policy.shape), self._p(lidar), self._p(inertial), self._p(last_action),
+                                                    self._p(mu), self._stream()), "te_drive_wingman_bf16")
+            return
         _lib.check(self.L.te_drive_wingman_shaped(self._h, int(wingman), self._p(fused_policy.params), C.byref(fused_policy.shape), self._p(lidar),
                                                   self._p(inertial), self._p(last_action), self._p(mu), self._stream()), "te_drive_wingman_shaped")
 

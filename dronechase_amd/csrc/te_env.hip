@@ -18,7 +18,7 @@
 // te_set_ally_actions, or with te_drive_wingman when a packed policy flies the ally: the kernels of a caller-driven
 // pursuer are te_wingman.hpp's.)
 // No MFMA: this is element-wise physics and byte streaming.  The MFMA kernels of the library are the policy's
-// inference, te_policy_act (te_policy.hpp) and te_drive_wingman's policy_drive_kernel (te_wingman.hpp), and its PPO gradient,
+// inference, te_policy_act (te_policy.hpp) and te_drive_wingman's policy_drive_kernel / policy_drive_bf16_kernel (te_wingman.hpp), and its PPO gradient,
 // te_policy_ppo_grad (te_policy_grad.hpp), the optimiser step, te_policy_adam_step (te_policy_opt.hpp), and the advantage arithmetic,
 // te_rollout_gae and te_adv_stats (te_rollout.hpp); none is part of te_step.
 //
@@ -1052,7 +1052,7 @@ static hipError_t set_lds_limits(const KernelPlan& k) {   // dynamic LDS beyond 
   return hipSuccess;
 }
 
-// The one launch of every policy kernel (the five tables below): kernel(args...) on ceil(rows / M) workgroups of the geometry the caller
+// The one launch of every policy kernel (the six tables below): kernel(args...) on ceil(rows / M) workgroups of the geometry the caller
 // read from the LDS plan that applies (pol_lds_plan for the fp32 tables, with kPolThreads; pol_lds_plan_bf16 / pol_grad_lds_plan_bf16 for
 // the bf16 ones).  A shape's LDS is above the 64 KB a launch gets by default: opt in once per (function, device), in the one `opted`
 // map; not a stream operation, so a capturing stream allows it.
@@ -1105,6 +1105,8 @@ static const PolKernel<PolicyIn, GradTileArgs> kPolicyGradKernels[POL_SHAPE_COUN
 static const PolKernel<PolicyBf16, PolicyIO> kPolicyActBf16Kernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_act_bf16_kernel);
 static const PolKernel<PolicyBf16, PolicyBf16, PolicyIn, GradTileArgsB> kPolicyGradBf16Kernels[POL_SHAPE_COUNT][2] =
     TE_POL_INSTANCES(policy_grad_bf16_tile_kernel);
+// te_drive_wingman_bf16's instances (te_wingman.hpp)
+static const PolKernel<PolicyBf16, PolicyIn, Params, int, float*> kPolicyDriveBf16Kernels[POL_SHAPE_COUNT][2] = TE_POL_INSTANCES(policy_drive_bf16_kernel);
 
 static std::string shape_text(const PolShape& s) {
   std::string t = "features_dim " + std::to_string(s.F) + ", hidden";
@@ -1850,23 +1852,29 @@ __attribute__((visibility("default"))) int te_policy_act_bf16(const float* param
                     action, logp, action_env, stream);
 }
 
-// te_drive_wingman and te_drive_wingman_shaped behind their shape checks
-static int drive_wingman(const char* fn, int shape_id, te_env* e, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar,
-                         float* inertial, float* last_action, float* mu, void* stream) {
+// The three drive entries behind their shape checks.  bf16: te_drive_wingman_bf16, which also takes weights_bf16 and launches the bf16
+// instance on its own LDS plan
+static int drive_wingman(const char* fn, bool bf16, int shape_id, te_env* e, int32_t wingman, const float* params, const uint16_t* weights_bf16,
+                         int32_t lidar_channels, float* lidar, float* inertial, float* last_action, float* mu, void* stream) {
   const std::string who = std::string(fn);
   if (!wingman_is_callers(e, wingman))
     return fail(who + ": this pursuer is not driven by the caller (exp05: cfg.ally_policy == TE_ALLY_EXTERNAL, pursuer 1; evaluation: the driver mask in cfg.evaluation)");
   if (!params || !lidar || !inertial || !last_action) return fail(who + ": params, lidar, inertial and last_action are required");
+  if (bf16 && !weights_bf16) return fail(who + ": weights_bf16 is required");
   if (lidar_channels != e->p.cfg.lidar_channels)
     return fail(who + ": lidar_channels (" + std::to_string(lidar_channels) + ") differs from the env's cfg.lidar_channels (" +
                 std::to_string(e->p.cfg.lidar_channels) + ")");
   if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
+  if (bf16 && ((uintptr_t)weights_bf16 & 15)) return fail(who + ": weights_bf16 must be 16-byte aligned");
   if (((uintptr_t)lidar & 15) || ((uintptr_t)last_action & 15)) return fail(who + ": lidar and last_action must be 16-byte aligned");
   if (((uintptr_t)inertial & 3) || ((uintptr_t)mu & 3)) return fail(who + ": inertial and mu must be 4-byte aligned");
   DeviceGuard guard(e->device);
   if (te_observe_wingman(e, wingman, lidar, inertial, last_action, nullptr, stream)) return 1;
   const PolicyIn in{lidar, inertial, last_action, nullptr, e->p.N};
   const PolShape shape = pol_shape(shape_id, lidar_channels);
+  if (bf16)
+    return policy_launch(kPolicyDriveBf16Kernels[shape_id][lidar_channels - 2], pol_geom(pol_lds_plan_bf16(shape)), e->p.N, stream,
+                         policy_params(shape, params), policy_weights(shape, weights_bf16), in, e->p, (int)wingman, mu);
   return policy_launch(kPolicyDriveKernels[shape_id][lidar_channels - 2], pol_geom(pol_lds_plan(shape)), e->p.N, stream, policy_params(shape, params),
                        in, e->p, (int)wingman, mu);
 }
@@ -1874,7 +1882,8 @@ static int drive_wingman(const char* fn, int shape_id, te_env* e, int32_t wingma
 __attribute__((visibility("default"))) int te_drive_wingman(te_env* e, int32_t wingman, const float* params, int32_t lidar_channels, float* lidar,
                                                             float* inertial, float* last_action, float* mu, void* stream) {
   if (!e) return fail("te_drive_wingman: null env");
-  return drive_wingman("te_drive_wingman", POL_SHAPE_DEFAULT, e, wingman, params, lidar_channels, lidar, inertial, last_action, mu, stream);
+  return drive_wingman("te_drive_wingman", false, POL_SHAPE_DEFAULT, e, wingman, params, nullptr, lidar_channels, lidar, inertial, last_action, mu,
+                       stream);
 }
 
 __attribute__((visibility("default"))) int te_drive_wingman_shaped(te_env* e, int32_t wingman, const float* params, const te_policy_shape* shape,
@@ -1882,7 +1891,18 @@ __attribute__((visibility("default"))) int te_drive_wingman_shaped(te_env* e, in
   if (!e) return fail("te_drive_wingman_shaped: null env");
   const int id = policy_shape_id(shape, "te_drive_wingman_shaped");
   if (id < 0) return 1;
-  return drive_wingman("te_drive_wingman_shaped", id, e, wingman, params, shape->lidar_channels, lidar, inertial, last_action, mu, stream);
+  return drive_wingman("te_drive_wingman_shaped", false, id, e, wingman, params, nullptr, shape->lidar_channels, lidar, inertial, last_action, mu,
+                       stream);
+}
+
+__attribute__((visibility("default"))) int te_drive_wingman_bf16(te_env* e, int32_t wingman, const float* params, const uint16_t* weights_bf16,
+                                                                 const te_policy_shape* shape, float* lidar, float* inertial, float* last_action,
+                                                                 float* mu, void* stream) {
+  if (!e) return fail("te_drive_wingman_bf16: null env");
+  const int id = policy_shape_id(shape, "te_drive_wingman_bf16");
+  if (id < 0) return 1;
+  return drive_wingman("te_drive_wingman_bf16", true, id, e, wingman, params, weights_bf16, shape->lidar_channels, lidar, inertial, last_action, mu,
+                       stream);
 }
 
 // The gradient entries behind their shape checks (fn: the caller's name in the messages; size_fn: the entry that tells the workspace's

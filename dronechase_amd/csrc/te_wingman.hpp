@@ -1,6 +1,6 @@
 // te_wingman.hpp — the caller-driven pursuer (exp05's ally, Evaluation_Task's "nn" drivers): its observation, its drive and its info
 // rows.  The C ABI on top of these kernels is te_env.hip's te_observe_wingman / te_observe_ally, te_set_wingman_actions /
-// te_set_ally_actions, te_drive_wingman and te_wingman_info.
+// te_set_ally_actions, te_drive_wingman / te_drive_wingman_bf16 and te_wingman_info.
 //
 // The observation is Exp05_vFinal_Task.compute_lw_observation (exp05_vFinal_task.py:265-292) of pursuer `me`: the LIDAR cell and range
 // of every other armed drone seen from the pursuer's IMU attitude, patched into a sphere of ones.  Same rules as the agent's sphere:
@@ -18,6 +18,7 @@
 
 #include "te_logic.hpp"
 #include "te_policy.hpp"
+#include "te_policy_bf16.hpp"
 
 namespace te {
 
@@ -168,6 +169,19 @@ __global__ __launch_bounds__(256) void set_ally_actions_kernel(Params p, int me,
   drive_caller_pursuer(v, me, reinterpret_cast<const float4*>(actions)[env]);
 }
 
+// The tail of both drive kernels, for the thread that computed row `env`'s mean MU[4] (in LDS): mu[env] for every row when mu is
+// non-null, then set_ally_actions_kernel's drive with the mean clamped to [-1, 1]^3 x [0, 1] where pursuer `me` is armed.
+TE_DEV void drive_with_mean(const Params& p, int me, int env, const float* MU, float* __restrict__ mu) {
+  if (mu) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) mu[(size_t)env * 4 + a] = MU[a];
+  }
+  const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
+  if (!v.gi(TE_D_ARMED, me)) return;
+  drive_caller_pursuer(v, me, make_float4(fmaxf(fminf(MU[0], 1.f), -1.f), fmaxf(fminf(MU[1], 1.f), -1.f), fmaxf(fminf(MU[2], 1.f), -1.f),
+                                          fmaxf(fminf(MU[3], 1.f), 0.f)));
+}
+
 // te_drive_wingman: the deterministic predict of the packed policy on pursuer `me`'s observation (te_observe_wingman's output,
 // read as te_policy_act reads its rows), then set_ally_actions_kernel's drive with the clamped mean.  pol_forward is the one
 // policy_act_kernel runs, so mu is bitwise te_policy_act's.  Every row is computed; rows of envs whose pursuer is dead keep
@@ -179,15 +193,22 @@ __global__ __launch_bounds__(kPolThreads) void policy_drive_kernel(PolicyParams 
   const int tid = threadIdx.x, env = blockIdx.x * M + tid;
   pol_forward<C, S>(P, in, pol_lds, blockIdx.x * M, PolNoSave{});
   if (tid >= M || env >= in.n) return;
-  const float* MU = pol_mu_lds<S>(pol_lds) + tid * 4;   // read back by the thread that computed it
-  if (mu) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) mu[(size_t)env * 4 + a] = MU[a];
-  }
-  const GView v{p.dstate, p.estate, p.D, p.Npad, env, p.cfg.n_pursuers};
-  if (!v.gi(TE_D_ARMED, me)) return;
-  drive_caller_pursuer(v, me, make_float4(fmaxf(fminf(MU[0], 1.f), -1.f), fmaxf(fminf(MU[1], 1.f), -1.f), fmaxf(fminf(MU[2], 1.f), -1.f),
-                                          fmaxf(fminf(MU[3], 1.f), 0.f)));
+  drive_with_mean(p, me, env, pol_mu_lds<S>(pol_lds) + tid * 4, mu);   // read back by the thread that computed it
+}
+
+// te_drive_wingman_bf16: the same with te_policy_act_bf16's forward (te_policy_bf16.hpp).  pol_forward_bf16 is the one
+// policy_act_bf16_kernel runs, on the same tile (pol_lds_plan_bf16: 32 rows of 256 threads for the default shape, 48 rows of 512
+// threads for the wide ones), so mu is bitwise te_policy_act_bf16's; the tail is policy_drive_kernel's.
+template <int C, int S = POL_SHAPE_DEFAULT>
+__global__ __launch_bounds__(pol_lds_plan_bf16(pol_shape(S, C)).threads) void policy_drive_bf16_kernel(PolicyParams P, PolicyBf16 Wb, PolicyIn in,
+                                                                                                      Params p, int me, float* __restrict__ mu) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pol_lds_b[];
+  constexpr PolLdsB lp = pol_lds_plan_bf16(pol_shape(S, C));
+  constexpr int M = lp.M;
+  const int tid = threadIdx.x, env = blockIdx.x * M + tid;
+  pol_forward_bf16<C, S>(P, Wb, in, pol_lds_b, blockIdx.x * M, PolNoSaveB{});
+  if (tid >= M || env >= in.n) return;
+  drive_with_mean(p, me, env, reinterpret_cast<const float*>(pol_lds_b) + lp.mu + tid * 4, mu);   // read back by the thread that computed it
 }
 
 // Evaluation_Task.compute_info (evaluation_task.py:553-574): (lw_kills, lw_alive, lw_munitions, current_wave, step) per pursuer

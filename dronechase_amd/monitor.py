@@ -222,7 +222,9 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 100, deterministic: bool
     PolicyDriver, or a PPO (its learner).  deterministic=True steps with mu clamped to [-1, 1]^3 x [0, 1] (through te_policy_act
     when the policy is fused), False with a clamped sample.  Caller-driven pursuers (exp05's ally, the evaluation task's driver
     mask) are flown by `wingman_policy` (a module or a FusedPolicy; default: a PPO's own wingman) with one drive_wingman call per
-    pursuer before every step, as PPO's rollout does.
+    pursuer before every step, as PPO's rollout does.  A FusedPolicy is passed through as it is, so the drive's precision follows the
+    object: FusedPolicy(module, precision="bf16"), or the wingman of a PPO with PPOConfig.wingman_bf16, flies through te_drive_wingman_bf16;
+    a module is packed in fp32.
     The host reads 4 bytes (the number of recorded episodes) every `poll_every` steps and never per step; steps taken after
     the last quota is met change nothing.  max_steps bounds the loop: if it is reached with fewer than n_eval_episodes recorded,
     RuntimeError says how many were.  Default 1 000 000 steps, far more than any task's episodes need (a stage03 episode is at most a

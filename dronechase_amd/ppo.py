@@ -24,7 +24,8 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
     instead of ~9 PyTorch launches per step, the minibatch's advantage mean and std as one te_adv_stats call (adv_stats below)
     into the two floats te_policy_ppo_grad reads, and "explained_variance" in update()'s log;
   * PPOConfig.wingman_driver / PPO(wingman_policy=...): exp05's ally (and the evaluation task's "nn" drivers) flown by a frozen
-    policy inside the rollout, one te_drive_wingman call per caller-driven pursuer before every te_step;
+    policy inside the rollout, one te_drive_wingman call per caller-driven pursuer before every te_step (PPOConfig.wingman_bf16:
+    te_drive_wingman_bf16, the bf16 MFMA forward in front of the same clamp and drive);
   * PPOConfig.episode_stats / PPO.evaluate: episode returns, lengths and final info rows accumulated on the device (monitor.py,
     te_monitor_step), and SB3's evaluate_policy over a separate evaluation env;
   * multi-GPU: one process per GPU, each with its own env shard; gradients are averaged with
@@ -236,12 +237,13 @@ class FusedPolicy:
     After bind_parameters() the module's parameters are views of the packed buffer and there is nothing left to repack.
     precision="bf16": forward and act go to te_policy_act_bf16 (bf16 operands on the bf16 MFMA, fp32 accumulation; the numerics
     contract is in include/threatengage.h).  The object then owns a second buffer, the weights rounded to bf16 (te_policy_pack_bf16),
-    at a stable address too; refresh() repacks it with one more launch, also after bind_parameters().  precision does not touch
+    at a stable address too; refresh() repacks it with one more launch, also after bind_parameters().  BatchedEnv.drive_wingman follows
+    `precision` too: a bf16 object flies its pursuer through te_drive_wingman_bf16 (PPOConfig.wingman_bf16).  precision does not touch
     ppo_grad.
     grad_precision="bf16": ppo_grad goes to te_policy_ppo_grad_bf16 (the same contract, extended to the backward), whose forward is
     bitwise te_policy_act_bf16's.  The object then owns weights_bf16 (shared with precision="bf16") and weights_bf16_t, the transposed
-    rounded weights (te_policy_pack_bf16_grad), both at stable addresses and both repacked by refresh(), also when bound.  forward and
-    act follow `precision` alone: precision="fp32", grad_precision="bf16" keeps the fp32 forward."""
+    rounded weights (te_policy_pack_bf16_grad), both at stable addresses and both repacked by refresh(), also when bound.  forward,
+    act and BatchedEnv.drive_wingman follow `precision` alone: precision="fp32", grad_precision="bf16" keeps the fp32 forward."""
 
     def __init__(self, policy: nn.Module, precision: str = "fp32", grad_precision: str = "fp32"):
         if precision not in ("fp32", "bf16"):
@@ -564,6 +566,15 @@ class PPOConfig:
     # call per pursuer (observe, deterministic forward, clamp, drive) runs before every te_step, in both collect paths
     wingman_driver: str = "none"
     wingman_sync_every: int = 1
+    # the wingmen's frozen policy through te_drive_wingman_bf16 (FusedPolicy(precision="bf16")): te_policy_act_bf16's forward in front of the
+    # same clamp and drive.  Needs a wingman driver: wingman_driver="snapshot" or PPO(..., wingman_policy=module).  sync_wingmen() repacks
+    # the bf16 weights in place with the fp32 ones, so the captured rollout graph flies them.  Independent of fused_forward_bf16 (the
+    # learner's launch).  Measured on the MI355X at 65 536 exp05 envs (profiles/wingman_bf16.json): the call takes 0.321 ms for
+    # the default shape, 0.645 ms for (128, 256, 512) and 0.630 ms for (512, 128, 256) against te_drive_wingman_shaped's 0.666 / 3.165 /
+    # 3.922 ms, and a graph-captured collect step with fused_forward_bf16 1.03 / 1.71 / 1.70 ms against 1.40 / 4.32 / 5.06 ms.  What it
+    # costs: over one rollout the ally's mean differs from the fp32 launch's on the same rows by 5e-5 to 6.5e-5 on average and 4.3e-4 at
+    # most, so the ally does not fly the fp32 trajectory bit for bit.  Off by default
+    wingman_bf16: bool = False
     # collect() also returns the statistics of the episodes that FINISHED during it (SB3's ep_rew_mean / ep_len_mean, plus the means of
     # the info row they ended with): an EpisodeMonitor (monitor.py, te_monitor_step) is fed the raw reward, done and info of every rollout
     # step on the device, one extra launch per step and one 80-byte host read per collect().  An episode still running at the end of a
@@ -686,6 +697,9 @@ class PPO:
         drv = self.cfg.wingman_driver
         if drv not in ("none", "snapshot"):
             raise ValueError(f"PPOConfig.wingman_driver must be 'none' or 'snapshot', not {drv!r}")
+        if self.cfg.wingman_bf16 and drv == "none" and wingman_policy is None:
+            raise ValueError("PPOConfig.wingman_bf16 is the wingman driver's forward with bf16 operands: it needs wingman_driver='snapshot' "
+                             "or PPO(..., wingman_policy=module)")
         caller_driven = ecfg is not None and (int(ecfg.ally_policy) == 3 or (int(ecfg.evaluation) >> 8) != 0)
         if caller_driven and drv == "none" and wingman_policy is None:
             # exp05 / Evaluation_Task "nn" drivers: somebody has to answer te_observe_wingman with te_set_wingman_actions
@@ -730,7 +744,7 @@ class PPO:
             if wingman_policy is None:
                 self._wingman_snapshot = True
                 wingman_policy = copy.deepcopy(self.policy).requires_grad_(False)
-            self.wingman = FusedPolicy(wingman_policy)
+            self.wingman = FusedPolicy(wingman_policy, precision="bf16" if self.cfg.wingman_bf16 else "fp32")
             if self.wingman.device != self.device:
                 raise ValueError(f"PPO: wingman_policy lives on {self.wingman.device}, the environment on {self.device}")
             if self.wingman.lidar_channels != int(ecfg.lidar_channels):
@@ -925,7 +939,9 @@ class PPO:
 
     def evaluate(self, env, n_eval_episodes: int = 100, deterministic: bool = True, **kwargs):
         """SB3 EvalCallback's evaluate_policy of the learner on a SEPARATE evaluation env (monitor.evaluate_policy: it is reset and
-        stepped; the training env is never touched): (episode_rewards, episode_lengths), raw rewards."""
+        stepped; the training env is never touched): (episode_rewards, episode_lengths), raw rewards.  Caller-driven pursuers are flown
+        by this PPO's own wingman object unless wingman_policy= says otherwise, in that object's precision (bf16 with
+        PPOConfig.wingman_bf16)."""
         from .monitor import evaluate_policy
 
         if getattr(env, "backend", env) is self.env:

@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define TE_ABI_VERSION 5   /* layout of te_config / the state blob.  Added since without a layout change: the task presets 10-12, TE_REWARD_L5_C1,
-                              bit 1 of te_config.evaluation (TE_EVAL_ORIGIN_RULE) */
+                              bit 1 of te_config.evaluation (TE_EVAL_ORIGIN_RULE), te_drive_wingman_bf16 */
 
 /* ---- tasks (reference env class each one mirrors) ----------------------- */
 enum {
@@ -520,6 +520,17 @@ int te_policy_pack_bf16(const float* params, const te_policy_shape* shape, uint1
 int te_policy_act_bf16(const float* params, const uint16_t* weights_bf16, const te_policy_shape* shape, int32_t n, const float* lidar,
                        const float* inertial, const float* last_action, const float* eps, float* mu, float* value, float* action,
                        float* logp, float* action_env, void* stream);
+
+/* te_drive_wingman_shaped with te_policy_act_bf16's numerics, opt-in, for every served shape and lidar_channels 2 and 3: the contract,
+ * arguments and checks of te_drive_wingman_shaped (above), plus weights_bf16, te_policy_pack_bf16's buffer for `params` (non-null, 16-byte
+ * aligned).  The forward is te_policy_act_bf16's on its own tile, so mu (optional, every row) is bitwise te_policy_act_bf16's, and the env
+ * state afterwards is bitwise the one of te_observe_wingman -> te_policy_act_bf16 (eps NULL) -> clamp -> te_set_wingman_actions.  The
+ * clamp and the drive are te_drive_wingman's, in fp32.  Every argument error returns non-zero before any launch with te_last_error
+ * starting "te_drive_wingman_bf16"; an unserved shape is refused with the served list.  Enqueues on `stream` only (no allocation, no
+ * host synchronisation): a HIP graph can capture it. */
+int te_drive_wingman_bf16(te_env* env, int32_t wingman, const float* params, const uint16_t* weights_bf16,
+                          const struct te_policy_shape* shape, float* lidar, float* inertial, float* last_action,
+                          float* mu, void* stream);
 
 /* te_policy_ppo_grad_bf16: te_policy_ppo_grad_shaped (below) with bf16 operands on v_mfma_f32_16x16x32_bf16 and fp32 accumulation, for
  * every served shape and lidar_channels 2 and 3; opt-in, the fp32 calls are unchanged.  The loss, the arguments, grad (fp32, packed),
