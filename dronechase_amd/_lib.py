@@ -128,6 +128,37 @@ def check(rc: int, what: str = "") -> None:
         raise TEError(f"{what}: {load().te_last_error().decode()}")
 
 
+def call(name: str, *args) -> None:
+    """The ABI entry `name` with `args`; a non-zero return is a TEError that names the entry."""
+    check(getattr(load(), name)(*args), name)
+
+
+def call_on(device, name: str, *args) -> None:
+    """call() for the entries that act on the current device and take the stream last (te_policy_*, te_rollout_gae, te_adv_stats,
+    te_monitor_*): on `device`, on PyTorch's current stream of it."""
+    import torch
+    with torch.cuda.device(device):
+        call(name, *args, torch.cuda.current_stream(device).cuda_stream)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def require_f32(who: str, name: str, t, shape, device, shown=None) -> None:
+    """Every float array of the policy's ABI calls: contiguous float32 of `shape` on `device` (`shown`: the shape as the message spells it)."""
+    import torch
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous float32 {shown or shape} tensor on {device}")
+
+
+def require_index(who: str, index, device) -> None:
+    """The minibatch index of te_policy_ppo_grad and te_adv_stats: None (every row), or contiguous 1-D int64 on `device`."""
+    import torch
+    if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != device or not index.is_contiguous()):
+        raise ValueError(f"{who}: index must be a contiguous 1-D int64 tensor on {device}")
+
+
 def default_config(task, **overrides) -> K.Config:
     """te_config_default(task) with keyword overrides (`quad__mass=...` reaches into te_quad_params; `quad_preset=1` swaps the
     whole quadrotor table with te_quad_preset before the other overrides apply)."""

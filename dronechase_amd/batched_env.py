@@ -9,7 +9,7 @@ import torch
 
 from . import _lib
 from . import config as K
-from .ppo import require_f32
+from ._lib import require_f32
 
 
 class BatchedEnv:
@@ -191,13 +191,9 @@ class BatchedEnv:
             raise ValueError(f"drive_wingman: the policy lives on {fused_policy.device}, the env on {self.device}")
         if mu is not None:
             require_f32("drive_wingman", "mu", mu, (self.N, 4), self.device, shown=f"[{self.N}, 4]")
-        if fused_policy.precision == "bf16":
-            _lib.check(self.L.te_drive_wingman_bf16(self._h, int(wingman), self._p(fused_policy.params), self._p(fused_policy.weights_bf16),
-                                                    C.byref(fused_policy.shape), self._p(lidar), self._p(inertial), self._p(last_action),
-                                                    self._p(mu), self._stream()), "te_drive_wingman_bf16")
-            return
-        _lib.check(self.L.te_drive_wingman_shaped(self._h, int(wingman), self._p(fused_policy.params), C.byref(fused_policy.shape), self._p(lidar),
-                                                  self._p(inertial), self._p(last_action), self._p(mu), self._stream()), "te_drive_wingman_shaped")
+        entry, weights = fused_policy.drive_entry
+        _lib.call(entry, self._h, int(wingman), *(self._p(w) for w in weights), C.byref(fused_policy.shape), self._p(lidar),
+                  self._p(inertial), self._p(last_action), self._p(mu), self._stream())
 
     def observe_ally(self):
         """exp05: the ally = pursuer 1 (Exp05_vFinal_Task.compute_lw_observation)."""

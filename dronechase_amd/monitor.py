@@ -68,9 +68,8 @@ class EpisodeMonitor:
         self.device = torch.device(device)
         self.on_gpu = self.device.type == "cuda"
         if self.on_gpu:
-            self.L = _lib.load()
             o = _lib.MonitorOffsets()
-            _lib.check(self.L.te_monitor_layout(self.N, self.R, C.byref(o)), "te_monitor_layout")
+            _lib.call("te_monitor_layout", self.N, self.R, C.byref(o))
             self._o = o
             self.buf = torch.empty(int(o.bytes), dtype=torch.uint8, device=self.device)
             self.device = self.buf.device        # "cuda" -> "cuda:N": the device the callers' tensors report
@@ -89,14 +88,10 @@ class EpisodeMonitor:
     def _args(self):
         return self.buf.data_ptr(), self.buf.numel(), self.N, self.R
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def reset(self) -> None:
         """Forget everything: partial episodes, the window, the records."""
         if self.on_gpu:
-            with torch.cuda.device(self.device):
-                _lib.check(self.L.te_monitor_init(*self._args(), self._stream()), "te_monitor_init")
+            _lib.call_on(self.device, "te_monitor_init", *self._args())
             return
         N, R = self.N, self.R
         self._s = dict(ret=np.zeros(N, np.float32), len=np.zeros(N, np.int32), episodes=np.zeros(N, np.int32),
@@ -113,8 +108,7 @@ class EpisodeMonitor:
             if tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
                 raise ValueError(f"EpisodeMonitor.step: {name} must be a contiguous {dt} {shape} tensor on {self.device}")
         if self.on_gpu:
-            with torch.cuda.device(self.device):
-                _lib.check(self.L.te_monitor_step(*self._args(), reward.data_ptr(), done.data_ptr(), info.data_ptr(), self._stream()), "te_monitor_step")
+            _lib.call_on(self.device, "te_monitor_step", *self._args(), reward.data_ptr(), done.data_ptr(), info.data_ptr())
             return
         s, w = self._s, self._s["window"]
         s["ret"] += reward.detach().numpy()          # float32 + float32: one rounding per step
@@ -139,8 +133,7 @@ class EpisodeMonitor:
         """The window's raw te_monitor_summary (a numpy record: count, sum_len, sum_info[4], sum_ret, sum_ret2, min_ret, max_ret,
         recorded).  One 80-byte host read; reset=True starts a new window (partial episodes carry over)."""
         if self.on_gpu:
-            with torch.cuda.device(self.device):
-                _lib.check(self.L.te_monitor_stats(*self._args(), self._summary.data_ptr(), 1 if reset else 0, self._stream()), "te_monitor_stats")
+            _lib.call_on(self.device, "te_monitor_stats", *self._args(), self._summary.data_ptr(), 1 if reset else 0)
             return self._summary.cpu().numpy().view(_SUMMARY)[0]
         out = self._s["window"].copy()
         if reset:

@@ -43,6 +43,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import config as K
+from ._lib import _ptr, require_f32, require_index    # require_f32: also this module's name for it (the callers' import)
 
 
 class LidarInertialActionPolicy(nn.Module):
@@ -135,7 +137,7 @@ def policy_param_words(lidar_channels: int, features_dim: int = DEFAULT_FEATURES
     """The words of the packed parameter buffer of a served shape (te_policy_param_words_shaped)."""
     shape = check_policy_shape(lidar_channels, features_dim, net_arch)
     out = C.c_size_t()
-    _lib.check(_lib.load().te_policy_param_words_shaped(C.byref(shape), C.byref(out)), "te_policy_param_words_shaped")
+    _lib.call("te_policy_param_words_shaped", C.byref(shape), C.byref(out))
     return int(out.value)
 
 
@@ -213,16 +215,6 @@ def load_sb3_policy(path_or_state_dict, lidar_shape=(3, 13, 26)) -> LidarInertia
     return policy
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
-def require_f32(who: str, name: str, t: torch.Tensor, shape, device: torch.device, shown: Optional[str] = None) -> None:
-    """Every float array of the policy's ABI calls: contiguous float32 of `shape` on `device` (`shown`: the shape as the message spells it)."""
-    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != device or not t.is_contiguous():
-        raise ValueError(f"{who}: {name} must be a contiguous float32 {shown or shape} tensor on {device}")
-
-
 GRAD_DEFAULT_ONLY = ("the gradient kernel te_policy_ppo_grad serves the default shape only (features_dim 256, net_arch (64, 64)): "
                      "PPOConfig.fused_update and fused_optimizer are not available for this policy; without them update() runs autograd.  "
                      "PPOConfig.fused_update_wide (with fused_update) asks for te_policy_ppo_grad_shaped, which serves every shape FusedPolicy does")
@@ -264,12 +256,20 @@ class FusedPolicy:
         self.params = torch.empty(words, dtype=torch.float32, device=self.device)
         self.weights_bf16 = self.weights_bf16_t = None
         half = C.c_size_t()
-        if precision == "bf16" or grad_precision == "bf16":
-            _lib.check(_lib.load().te_policy_bf16_words(C.byref(self.shape), C.byref(half)), "te_policy_bf16_words")
+        bf16, grad_bf16 = precision == "bf16", grad_precision == "bf16"
+        if bf16 or grad_bf16:
+            _lib.call("te_policy_bf16_words", C.byref(self.shape), C.byref(half))
             self.weights_bf16 = torch.empty(int(half.value), dtype=torch.int16, device=self.device)
-        if grad_precision == "bf16":
-            _lib.check(_lib.load().te_policy_bf16_grad_words(C.byref(self.shape), C.byref(half)), "te_policy_bf16_grad_words")
+        if grad_bf16:
+            _lib.call("te_policy_bf16_grad_words", C.byref(self.shape), C.byref(half))
             self.weights_bf16_t = torch.empty(int(half.value), dtype=torch.int16, device=self.device)
+        # the one place that tells fp32 from bf16: per kind of call the entry and its leading weight arguments.  A bf16 entry takes the
+        # shaped entry's arguments with the rounded weights inserted after params (include/threatengage.h)
+        fp32, rounded = (self.params,), (self.params, self.weights_bf16)
+        self.act_entry = ("te_policy_act_bf16", rounded) if bf16 else ("te_policy_act_shaped", fp32)
+        self.drive_entry = ("te_drive_wingman_bf16", rounded) if bf16 else ("te_drive_wingman_shaped", fp32)     # BatchedEnv.drive_wingman
+        self.grad_entry = ("te_policy_ppo_grad_bf16", rounded + (self.weights_bf16_t,)) if grad_bf16 else ("te_policy_ppo_grad_shaped", fp32)
+        self.grad_ws_entry = "te_policy_grad_bf16_workspace_bytes" if grad_bf16 else "te_policy_grad_workspace_bytes_shaped"
         self.bound = False
         self.refresh()
 
@@ -277,13 +277,9 @@ class FusedPolicy:
         if not self.bound:      # bound: the parameters ARE the buffer (and torch.cat(out=) onto its own inputs raises)
             pack_policy(self.policy, out=self.params)
         if self.weights_bf16 is not None:       # the fp32 buffer is the master copy: round it again, in place, on the current stream
-            with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                _lib.check(_lib.load().te_policy_pack_bf16(self.params.data_ptr(), C.byref(self.shape), self.weights_bf16.data_ptr(), stream),
-                           "te_policy_pack_bf16")
-                if self.weights_bf16_t is not None:
-                    _lib.check(_lib.load().te_policy_pack_bf16_grad(self.params.data_ptr(), C.byref(self.shape), self.weights_bf16_t.data_ptr(),
-                                                                    stream), "te_policy_pack_bf16_grad")
+            _lib.call_on(self.device, "te_policy_pack_bf16", self.params.data_ptr(), C.byref(self.shape), self.weights_bf16.data_ptr())
+        if self.weights_bf16_t is not None:
+            _lib.call_on(self.device, "te_policy_pack_bf16_grad", self.params.data_ptr(), C.byref(self.shape), self.weights_bf16_t.data_ptr())
 
     @torch.no_grad()
     def bind_parameters(self) -> None:
@@ -339,17 +335,11 @@ class FusedPolicy:
                     continue
                 raise ValueError(f"FusedPolicy.ppo_grad: {name} is required")
             require_f32("FusedPolicy.ppo_grad", name, t, shape, self.device)
-        if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != self.device or not index.is_contiguous()):
-            raise ValueError(f"FusedPolicy.ppo_grad: index must be a contiguous 1-D int64 tensor on {self.device}")
+        require_index("FusedPolicy.ppo_grad", index, self.device)
         if b == 0:
             raise ValueError("FusedPolicy.ppo_grad: the minibatch is empty")
-        lib = _lib.load()
         need = C.c_size_t()
-        bf16 = self.grad_precision == "bf16"
-        if bf16:
-            _lib.check(lib.te_policy_grad_bf16_workspace_bytes(C.byref(self.shape), b, C.byref(need)), "te_policy_grad_bf16_workspace_bytes")
-        else:
-            _lib.check(lib.te_policy_grad_workspace_bytes_shaped(C.byref(self.shape), b, C.byref(need)), "te_policy_grad_workspace_bytes_shaped")
+        _lib.call(self.grad_ws_entry, C.byref(self.shape), b, C.byref(need))
         ws = getattr(self, "_grad_ws", None)
         if ws is None or ws.numel() < need.value:
             if torch.cuda.is_current_stream_capturing():
@@ -357,21 +347,11 @@ class FusedPolicy:
                                    "call once with this minibatch size before capture")
             self._grad_ws = None           # free the old workspace before the larger one is allocated
             ws = self._grad_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if bf16:
-                _lib.check(lib.te_policy_ppo_grad_bf16(self.params.data_ptr(), self.weights_bf16.data_ptr(), self.weights_bf16_t.data_ptr(),
-                                                       C.byref(self.shape), b, _ptr(index), lidar.data_ptr(), inertial.data_ptr(),
-                                                       last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(),
-                                                       ret.data_ptr(), _ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef),
-                                                       grad_out.data_ptr(), stats_out.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                           "te_policy_ppo_grad_bf16")
-                return
-            _lib.check(lib.te_policy_ppo_grad_shaped(self.params.data_ptr(), C.byref(self.shape), b, _ptr(index), lidar.data_ptr(),
-                                                     inertial.data_ptr(), last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(),
-                                                     adv.data_ptr(), ret.data_ptr(), _ptr(adv_mean_std), float(clip), float(vf_coef),
-                                                     float(ent_coef), grad_out.data_ptr(), stats_out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     stream), "te_policy_ppo_grad_shaped")
+        entry, weights = self.grad_entry
+        _lib.call_on(self.device, entry, *(w.data_ptr() for w in weights), C.byref(self.shape), b, _ptr(index), lidar.data_ptr(),
+                     inertial.data_ptr(), last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                     _ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef), grad_out.data_ptr(), stats_out.data_ptr(),
+                     ws.data_ptr(), ws.numel())
 
     def _call(self, obs, eps, outs):
         lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
@@ -380,15 +360,9 @@ class FusedPolicy:
                                ("last_action", last_action, (n, 4)), ("eps", eps, (n, 4))):
             if t is not None:
                 require_f32("FusedPolicy", name, t, shape, self.device)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            if self.precision == "bf16":
-                _lib.check(_lib.load().te_policy_act_bf16(self.params.data_ptr(), self.weights_bf16.data_ptr(), C.byref(self.shape), n,
-                                                          lidar.data_ptr(), inertial.data_ptr(), last_action.data_ptr(), _ptr(eps),
-                                                          *(_ptr(o) for o in outs), stream), "te_policy_act_bf16")
-                return
-            _lib.check(_lib.load().te_policy_act_shaped(self.params.data_ptr(), C.byref(self.shape), n, lidar.data_ptr(), inertial.data_ptr(),
-                                                        last_action.data_ptr(), _ptr(eps), *(_ptr(o) for o in outs), stream), "te_policy_act_shaped")
+        entry, weights = self.act_entry
+        _lib.call_on(self.device, entry, *(w.data_ptr() for w in weights), C.byref(self.shape), n, lidar.data_ptr(), inertial.data_ptr(),
+                     last_action.data_ptr(), _ptr(eps), *(_ptr(o) for o in outs))
 
     def forward(self, obs: Dict[str, torch.Tensor]):
         """(mu [N, 4], value [N]) of the module's forward."""
@@ -421,7 +395,7 @@ class PackedAdam:
         self.fused_policy, self.lr, self.betas, self.eps = fused_policy, float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.words = fused_policy.params.numel()
         need = C.c_size_t()
-        _lib.check(_lib.load().te_policy_opt_state_bytes(self.words, C.byref(need)), "te_policy_opt_state_bytes")
+        _lib.call("te_policy_opt_state_bytes", self.words, C.byref(need))
         self.state = torch.zeros(int(need.value) // 4, dtype=torch.float32, device=fused_policy.device)
         a = (self.words + 3) // 4 * 4            # m and v start on 16-byte boundaries behind the 64-byte header
         self.step_count = self.state[0:1].view(torch.int32)    # views of the state: reading them costs no host synchronisation
@@ -433,11 +407,8 @@ class PackedAdam:
         grad_scale multiplies the gradient before the norm and the update (1 / world_size after an all-reduce)."""
         f = self.fused_policy
         require_f32("PackedAdam.step", "grad", grad, (self.words,), f.device)
-        with torch.cuda.device(f.device):
-            stream = torch.cuda.current_stream(f.device).cuda_stream
-            _lib.check(_lib.load().te_policy_adam_step(f.params.data_ptr(), grad.data_ptr(), self.state.data_ptr(), self.state.numel() * 4,
-                                                       self.words, self.lr, self.betas[0], self.betas[1], self.eps, float(max_grad_norm),
-                                                       float(grad_scale), stream), "te_policy_adam_step")
+        _lib.call_on(f.device, "te_policy_adam_step", f.params.data_ptr(), grad.data_ptr(), self.state.data_ptr(), self.state.numel() * 4,
+                     self.words, self.lr, self.betas[0], self.betas[1], self.eps, float(max_grad_norm), float(grad_scale))
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         return {"state": self.state.clone()}
@@ -453,7 +424,7 @@ class PackedAdam:
 def adv_stats_workspace(n: int, device) -> torch.Tensor:
     """The workspace of adv_stats for up to n elements (te_adv_stats_workspace_bytes is monotone in n)."""
     need = C.c_size_t()
-    _lib.check(_lib.load().te_adv_stats_workspace_bytes(int(n), C.byref(need)), "te_adv_stats_workspace_bytes")
+    _lib.call("te_adv_stats_workspace_bytes", int(n), C.byref(need))
     return torch.empty(int(need.value), dtype=torch.uint8, device=device)
 
 
@@ -467,15 +438,11 @@ def adv_stats(x: torch.Tensor, index: Optional[torch.Tensor], out: torch.Tensor,
     if x.dim() != 1 or x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError("adv_stats: x must be a contiguous 1-D float32 tensor")
     require_f32("adv_stats", "out", out, (2,), dev)
-    if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or index.device != dev or not index.is_contiguous()):
-        raise ValueError(f"adv_stats: index must be a contiguous 1-D int64 tensor on {dev}")
+    require_index("adv_stats", index, dev)
     if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
         raise ValueError(f"adv_stats: workspace must be a contiguous uint8 tensor on {dev} (adv_stats_workspace)")
     n = x.numel() if index is None else index.numel()
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.load().te_adv_stats(x.data_ptr(), _ptr(index), n, out.data_ptr(), workspace.data_ptr(), workspace.numel(), stream),
-                   "te_adv_stats")
+    _lib.call_on(dev, "te_adv_stats", x.data_ptr(), _ptr(index), n, out.data_ptr(), workspace.data_ptr(), workspace.numel())
 
 
 class PolicyDriver:
@@ -618,14 +585,24 @@ class PPOConfig:
     fused_update_bf16: bool = False
 
     def __post_init__(self):
-        if self.fused_update_bf16 and not self.fused_update:
-            raise ValueError("PPOConfig.fused_update_bf16 is fused_update's call with bf16 operands: it needs fused_update")
-        if self.fused_optimizer and not self.fused_update:
-            raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
-        if self.fused_update_wide and not self.fused_update:
-            raise ValueError("PPOConfig.fused_update_wide widens fused_update to every served shape: it needs fused_update")
-        if self.fused_forward_bf16 and not self.fused_forward:
-            raise ValueError("PPOConfig.fused_forward_bf16 is fused_forward's launch with bf16 operands: it needs fused_forward")
+        for switch in SWITCH_NEEDS:
+            refusal = missing_switch(self, switch)
+            if refusal:
+                raise ValueError(refusal)
+
+
+# switch: (the switch it needs, what it is to it), in the order PPOConfig checks them.  PPO checks them again, in its own order
+# (PPO._refusal), for a switch set on the object after PPOConfig's own check
+SWITCH_NEEDS = {"fused_update_bf16": ("fused_update", "is fused_update's call with bf16 operands"),
+                "fused_optimizer": ("fused_update", "steps on te_policy_ppo_grad's packed gradient"),
+                "fused_update_wide": ("fused_update", "widens fused_update to every served shape"),
+                "fused_forward_bf16": ("fused_forward", "is fused_forward's launch with bf16 operands")}
+
+
+def missing_switch(cfg: PPOConfig, switch: str) -> Optional[str]:
+    """The refusal of `switch` when it is set without the switch it needs; None otherwise."""
+    needs, what = SWITCH_NEEDS[switch]
+    return f"PPOConfig.{switch} {what}: it needs {needs}" if getattr(cfg, switch) and not getattr(cfg, needs) else None
 
 
 class RolloutBuffer:
@@ -658,11 +635,8 @@ class RolloutBuffer:
             if dev.type != "cuda":
                 raise ValueError("RolloutBuffer.finish(fused=True) runs the HIP kernel te_rollout_gae: the buffer must live on a GPU")
             require_f32("RolloutBuffer.finish", "last_value", last_value, (N,), dev)
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _lib.check(_lib.load().te_rollout_gae(T, N, self.rewards.data_ptr(), self.values.data_ptr(), self.dones.data_ptr(),
-                                                      last_value.data_ptr(), float(gamma), float(lam), self.adv.data_ptr(),
-                                                      self.ret.data_ptr(), stream), "te_rollout_gae")
+            _lib.call_on(dev, "te_rollout_gae", T, N, self.rewards.data_ptr(), self.values.data_ptr(), self.dones.data_ptr(),
+                         last_value.data_ptr(), float(gamma), float(lam), self.adv.data_ptr(), self.ret.data_ptr())
             return
         gae = torch.zeros_like(last_value)
         nxt = last_value
@@ -681,7 +655,11 @@ def caller_driven_pursuers(ecfg) -> List[int]:
     if ecfg is None:
         return []
     mask = (int(ecfg.evaluation) & 0xFFFFFFFF) >> 8
-    return [p for p in range(int(ecfg.n_pursuers)) if (int(ecfg.ally_policy) == 3 and p == 1) or (mask >> p) & 1]
+    return [p for p in range(int(ecfg.n_pursuers)) if (int(ecfg.ally_policy) == K.ALLY_EXTERNAL and p == 1) or (mask >> p) & 1]
+
+
+LOSS_KEYS = ("pg_loss", "v_loss", "entropy", "clip_frac")        # update()'s log, in the order of te_policy_ppo_grad's stats_out
+EV_KEYS = ("adv_mean", "adv_std", "ret_mean", "ret_std")         # PPO._ev_stats: read with the log, folded into "explained_variance"
 
 
 class PPO:
@@ -694,39 +672,13 @@ class PPO:
         self.device = env.device
         ecfg = getattr(env, "cfg", None)
         self.wingmen = caller_driven_pursuers(ecfg)
-        drv = self.cfg.wingman_driver
-        if drv not in ("none", "snapshot"):
-            raise ValueError(f"PPOConfig.wingman_driver must be 'none' or 'snapshot', not {drv!r}")
-        if self.cfg.wingman_bf16 and drv == "none" and wingman_policy is None:
-            raise ValueError("PPOConfig.wingman_bf16 is the wingman driver's forward with bf16 operands: it needs wingman_driver='snapshot' "
-                             "or PPO(..., wingman_policy=module)")
-        caller_driven = ecfg is not None and (int(ecfg.ally_policy) == 3 or (int(ecfg.evaluation) >> 8) != 0)
-        if caller_driven and drv == "none" and wingman_policy is None:
-            # exp05 / Evaluation_Task "nn" drivers: somebody has to answer te_observe_wingman with te_set_wingman_actions
-            # before every te_step; this rollout loop does not, and the wingman would fly a stale set-point
-            raise ValueError("PPO drives the agent only: an environment with caller-driven wingmen (exp05, evaluation driver mask) "
-                             "needs its wingman driver in the loop (ThreatEngageVecEnv.update_model), not this rollout")
-        if drv != "none" or wingman_policy is not None:
-            if not self.wingmen:
-                raise ValueError("PPO: a wingman driver was given, but this environment has no caller-driven pursuer "
-                                 "(exp05's ally or cfg.evaluation's driver mask)")
-            if drv == "snapshot" and wingman_policy is not None:
-                raise ValueError("PPO: wingman_driver='snapshot' flies a copy of the learner; pass wingman_policy with wingman_driver='none'")
-            if self.device.type != "cuda":
-                raise ValueError("PPO's wingman driver runs the HIP kernels of te_drive_wingman: it needs a GPU device")
-            if int(self.cfg.wingman_sync_every) < 1:
-                raise ValueError("PPOConfig.wingman_sync_every must be >= 1")
         torch.manual_seed(seed)
-        self.policy = (policy or LidarInertialActionPolicy(lidar_shape=tuple(env.lidar.shape[1:]), features_dim=self.cfg.features_dim,
-                                                           net_arch=self.cfg.net_arch)).to(self.device)
-        if self.cfg.fused_update_wide and not self.cfg.fused_update:    # set after PPOConfig's own check
-            raise ValueError("PPOConfig.fused_update_wide widens fused_update to every served shape: it needs fused_update")
-        if self.cfg.fused_update_bf16 and not self.cfg.fused_update:    # set after PPOConfig's own check
-            raise ValueError("PPOConfig.fused_update_bf16 is fused_update's call with bf16 operands: it needs fused_update")
-        if (self.cfg.fused_update or self.cfg.fused_optimizer) and not is_default_shape(*policy_shape(self.policy)[1:]):
-            if not self.cfg.fused_update_wide:
-                raise ValueError(GRAD_DEFAULT_ONLY)
-            check_policy_shape(*policy_shape(self.policy))      # an unserved shape: the ValueError that lists the served ones
+        self.policy = policy or LidarInertialActionPolicy(lidar_shape=tuple(env.lidar.shape[1:]), features_dim=self.cfg.features_dim,
+                                                          net_arch=self.cfg.net_arch)
+        refusal = self._refusal(wingman_policy is not None)      # before anything is allocated on the env's device or asked of the env
+        if refusal:
+            raise ValueError(refusal)
+        self.policy = self.policy.to(self.device)
         fused = bool(self.cfg.fast_learner) and self.device.type == "cuda"
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=self.cfg.learning_rate, eps=1e-5, **({"fused": True} if fused else {}))
         shapes = {"lidar": tuple(env.lidar.shape[1:]), "inertial_data": (env.inertial.shape[1],), "last_action": (4,)}
@@ -763,18 +715,6 @@ class PPO:
             p.grad = self._flat_grad[off:off + p.numel()].view_as(p)
             off += p.numel()
         env.reset()
-        if self.cfg.fused_forward and self.device.type != "cuda":
-            raise ValueError("PPOConfig.fused_forward runs the HIP kernel te_policy_act: it needs a GPU device")
-        if self.cfg.fused_optimizer and self.device.type != "cuda":
-            raise ValueError("PPOConfig.fused_optimizer runs the HIP kernels of te_policy_adam_step: it needs a GPU device")
-        if self.cfg.fused_update and self.device.type != "cuda":
-            raise ValueError("PPOConfig.fused_update runs the HIP kernels of te_policy_ppo_grad: it needs a GPU device")
-        if self.cfg.fused_advantages and self.device.type != "cuda":
-            raise ValueError("PPOConfig.fused_advantages runs the HIP kernels of te_rollout_gae and te_adv_stats: it needs a GPU device")
-        if self.cfg.fused_optimizer and not self.cfg.fused_update:      # set after PPOConfig's own check
-            raise ValueError("PPOConfig.fused_optimizer steps on te_policy_ppo_grad's packed gradient: it needs fused_update")
-        if self.cfg.fused_forward_bf16 and not self.cfg.fused_forward:      # set after PPOConfig's own check
-            raise ValueError("PPOConfig.fused_forward_bf16 is fused_forward's launch with bf16 operands: it needs fused_forward")
         precisions = dict(precision="bf16" if self.cfg.fused_forward_bf16 else "fp32",
                           grad_precision="bf16" if self.cfg.fused_update_bf16 else "fp32")     # one object serves both: the bf16 weights are shared
         self.fused = FusedPolicy(self.policy, **precisions) if self.cfg.fused_forward else None
@@ -794,6 +734,48 @@ class PPO:
             from .monitor import EpisodeMonitor
             self.monitor = EpisodeMonitor(env.N, self.device, n_records=0)
         self.num_timesteps = 0
+
+    def _refusal(self, wingman_given: bool) -> Optional[str]:
+        """Why this config, env and policy module cannot be trained together (the ValueError's text), or None: every rule that needs
+        no more than them and whether a wingman_policy was given, the first that fails.  Reads only; nothing is allocated."""
+        c, drv, on_gpu = self.cfg, self.cfg.wingman_driver, self.device.type == "cuda"
+        if drv not in ("none", "snapshot"):
+            return f"PPOConfig.wingman_driver must be 'none' or 'snapshot', not {drv!r}"
+        driver = drv != "none" or wingman_given
+        if c.wingman_bf16 and not driver:
+            return ("PPOConfig.wingman_bf16 is the wingman driver's forward with bf16 operands: it needs wingman_driver='snapshot' "
+                    "or PPO(..., wingman_policy=module)")
+        if self.wingmen and not driver:
+            # exp05 / Evaluation_Task "nn" drivers: somebody has to answer te_observe_wingman with te_set_wingman_actions
+            # before every te_step; this rollout loop does not, and the wingman would fly a stale set-point
+            return ("PPO drives the agent only: an environment with caller-driven wingmen (exp05, evaluation driver mask) "
+                    "needs its wingman driver in the loop (ThreatEngageVecEnv.update_model), not this rollout")
+        if driver:
+            if not self.wingmen:
+                return ("PPO: a wingman driver was given, but this environment has no caller-driven pursuer "
+                        "(exp05's ally or cfg.evaluation's driver mask)")
+            if drv == "snapshot" and wingman_given:
+                return "PPO: wingman_driver='snapshot' flies a copy of the learner; pass wingman_policy with wingman_driver='none'"
+            if not on_gpu:
+                return "PPO's wingman driver runs the HIP kernels of te_drive_wingman: it needs a GPU device"
+            if int(c.wingman_sync_every) < 1:
+                return "PPOConfig.wingman_sync_every must be >= 1"
+        early = missing_switch(c, "fused_update_wide") or missing_switch(c, "fused_update_bf16")     # set after PPOConfig's own check
+        if early:
+            return early
+        if (c.fused_update or c.fused_optimizer) and not is_default_shape(*policy_shape(self.policy)[1:]):
+            if not c.fused_update_wide:
+                return GRAD_DEFAULT_ONLY
+            try:
+                check_policy_shape(*policy_shape(self.policy))      # an unserved shape: the text that lists the served ones
+            except ValueError as e:
+                return str(e)
+        for switch, runs in (("fused_forward", "the HIP kernel te_policy_act"), ("fused_optimizer", "the HIP kernels of te_policy_adam_step"),
+                             ("fused_update", "the HIP kernels of te_policy_ppo_grad"),
+                             ("fused_advantages", "the HIP kernels of te_rollout_gae and te_adv_stats")):
+            if getattr(c, switch) and not on_gpu:
+                return f"PPOConfig.{switch} runs {runs}: it needs a GPU device"
+        return missing_switch(c, "fused_optimizer") or missing_switch(c, "fused_forward_bf16")      # set after PPOConfig's own check
 
     def sync_wingmen(self) -> None:
         """Repack the wingmen's frozen policy in place: the learner's current weights with wingman_driver='snapshot', the given
@@ -861,8 +843,6 @@ class PPO:
     @torch.no_grad()
     def _collect_graph(self) -> Dict[str, float]:
         b, c = self.buf, self.cfg
-        if self._obs is None:
-            self._obs = dict(zip(("lidar", "inertial_data", "last_action"), self.env.observe()))
         if not hasattr(self, "_graph"):
             self._capture_step()
         ep_rew = torch.zeros((), device=self.device); ep_n = torch.zeros((), dtype=torch.int64, device=self.device)
@@ -887,6 +867,8 @@ class PPO:
             self.fused.refresh()
         if self._wingman_snapshot and self._updates_since_sync >= self.cfg.wingman_sync_every:
             self.sync_wingmen()
+        if self._obs is None:
+            self._obs = dict(zip(("lidar", "inertial_data", "last_action"), self.env.observe()))
         if self.cfg.use_graph and self.device.type == "cuda":
             return self._collect_graph()
         return self._collect_eager()
@@ -898,8 +880,6 @@ class PPO:
         loop.  The observation after the last step goes to the env's own buffers and seeds slot 0 of the next rollout."""
         b, c = self.buf, self.cfg
         ep_rew = torch.zeros((), device=self.device); ep_n = torch.zeros((), dtype=torch.int64, device=self.device)
-        if self._obs is None:
-            self._obs = dict(zip(("lidar", "inertial_data", "last_action"), self.env.observe()))
         for k in b.obs:
             b.obs[k][0].copy_(self._obs[k])
         for t in range(c.n_steps):
@@ -955,7 +935,8 @@ class PPO:
         obs = {k: flat(v) for k, v in b.obs.items()}
         actions, old_logp, adv, ret = flat(b.actions), flat(b.logp), flat(b.adv), flat(b.ret)
         # running sums stay on the device: one host read per update(), not four per minibatch (each float() drains the stream)
-        acc = torch.zeros(5 if c.fused_optimizer else 4, device=self.device)   # fused_optimizer: + the gradient's norm before clipping
+        keys = LOSS_KEYS + (("grad_norm",) if c.fused_optimizer else ())      # grad_norm: the gradient's norm before clipping
+        acc = torch.zeros(len(keys), device=self.device)
         n_batches = 0
         if c.fused_advantages:          # explained_variance's two stds, on the device: read with the accumulators below
             adv_stats(adv, None, self._ev_stats[0:2], self._adv_ws)
@@ -967,9 +948,9 @@ class PPO:
                 idx = perm[s:s + c.batch_size]
                 if self.fused_grad is not None:
                     self._fused_minibatch(obs, idx, actions, old_logp, adv, ret)
-                    acc[:4] += self._grad_stats
+                    acc[:len(LOSS_KEYS)] += self._grad_stats
                     if c.fused_optimizer:
-                        acc[4:] += self.opt.grad_norm
+                        acc[len(LOSS_KEYS):] += self.opt.grad_norm
                     n_batches += 1
                     continue
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
@@ -986,31 +967,40 @@ class PPO:
                 loss = pg + c.vf_coef * vl - c.ent_coef * ent
                 self._flat_grad.zero_()          # the parameters' .grad are views of it: backward accumulates in place
                 loss.backward()
-                if self.distributed:             # the system's only collective: mean gradient over the ranks, one bucket
-                    torch.distributed.all_reduce(self._flat_grad)
-                    self._flat_grad.div_(torch.distributed.get_world_size())
-                nn.utils.clip_grad_norm_(self.policy.parameters(), c.max_grad_norm)
-                self.opt.step()
+                self._step()
                 with torch.no_grad():
                     acc += torch.stack((pg.detach(), vl.detach(), ent.detach(), ((ratio - 1).abs() > c.clip_range).float().mean()))
                 n_batches += 1
         means = acc / max(n_batches, 1)
         if c.fused_advantages:
-            means = torch.cat((means, self._ev_stats))
-        pg_s, vl_s, ent_s, clip_s, *rest = means.tolist()
+            keys, means = keys + EV_KEYS, torch.cat((means, self._ev_stats))
+        out = dict(zip(keys, means.tolist()))      # the one host read
         self._updates_since_sync += 1
-        out = {"pg_loss": pg_s, "v_loss": vl_s, "entropy": ent_s, "clip_frac": clip_s}
-        if c.fused_optimizer:
-            out["grad_norm"] = rest[0]
         if c.fused_advantages:          # ret - values is the advantage: 1 - Var(adv) / Var(ret), SB3's explained_variance
-            std_adv, std_ret = rest[-3], rest[-1]
+            _, std_adv, _, std_ret = (out.pop(k) for k in EV_KEYS)
             out["explained_variance"] = float("nan") if std_ret == 0.0 else 1.0 - (std_adv * std_adv) / (std_ret * std_ret)
         return out
 
+    def _step(self) -> None:
+        """The tail of every minibatch, on the gradient in the flat bucket: the system's only collective (the mean gradient over the
+        ranks, one bucket), clipping and the optimiser's step.  fused_optimizer: the all-reduce and one te_policy_adam_step call on
+        the buffer the next gradient reads (no repack, and no division: grad_scale)."""
+        c = self.cfg
+        world = 1
+        if self.distributed:
+            torch.distributed.all_reduce(self._flat_grad)
+            world = torch.distributed.get_world_size()
+        if c.fused_optimizer:
+            self.opt.step(self._flat_grad, c.max_grad_norm, grad_scale=1.0 / world)
+            return
+        if self.distributed:
+            self._flat_grad.div_(world)
+        nn.utils.clip_grad_norm_(self.policy.parameters(), c.max_grad_norm)
+        self.opt.step()
+
     def _fused_minibatch(self, obs, idx, actions, old_logp, adv, ret) -> None:
         """One minibatch of update() with fused_update: the gradient of the loss straight into the flat gradient bucket by
-        te_policy_ppo_grad, then the same all-reduce, clipping and Adam step as the autograd path; with fused_optimizer the all-reduce
-        and one te_policy_adam_step call on the buffer the next gradient reads (no repack, no division: grad_scale)."""
+        te_policy_ppo_grad, then the autograd path's tail (_step)."""
         c = self.cfg
         self.fused_grad.refresh()            # Adam moved the weights: repack them (one 0.94 MB device copy; nothing when bound)
         if c.fused_advantages:
@@ -1021,18 +1011,7 @@ class PPO:
             ms = torch.stack((a.mean(), a.std()))
         self.fused_grad.ppo_grad(obs, idx, actions, old_logp, adv, ret, ms, c.clip_range, c.vf_coef, c.ent_coef,
                                  self._flat_grad, self._grad_stats)
-        if c.fused_optimizer:
-            world = 1
-            if self.distributed:
-                torch.distributed.all_reduce(self._flat_grad)
-                world = torch.distributed.get_world_size()
-            self.opt.step(self._flat_grad, c.max_grad_norm, grad_scale=1.0 / world)
-            return
-        if self.distributed:
-            torch.distributed.all_reduce(self._flat_grad)
-            self._flat_grad.div_(torch.distributed.get_world_size())
-        nn.utils.clip_grad_norm_(self.policy.parameters(), c.max_grad_norm)
-        self.opt.step()
+        self._step()
 
     def learn(self, total_timesteps: int, log=None):
         while self.num_timesteps < total_timesteps:

@@ -8,6 +8,21 @@ import pytest
 DEFAULT = (256, (64, 64))      # (features_dim, net_arch) of the default policy
 
 
+class StubEnv:
+    """What PPO.__init__ reads of an environment, on the CPU (no stepping, no GPU): `task`'s config (None: no cfg, as a backend without
+    one) for n envs.  `resets` counts the reset() calls: a PPO(...) that refuses must leave it at 0."""
+
+    def __init__(self, task="stage03", n=4):
+        import torch
+        from dronechase_amd import default_config
+        self.cfg = None if task is None else default_config(task, n_envs=n)
+        self.N, self.device, self.resets = n, torch.device("cpu"), 0
+        self.lidar, self.inertial = torch.zeros(n, 3, 13, 26), torch.zeros(n, 15)
+
+    def reset(self):
+        self.resets += 1
+
+
 def _gpu():
     import torch
     if not torch.cuda.is_available():

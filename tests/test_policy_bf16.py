@@ -31,7 +31,7 @@ import os
 
 import pytest
 
-from tests._policy_cases import _gpu, _shape
+from tests._policy_cases import StubEnv, _gpu, _shape
 
 DEFAULT = (256, (64, 64))
 BO = (512, (128, 256, 512))
@@ -183,25 +183,12 @@ def test_switches_need_their_base(lib):
         PolicyDriver(p, fused=False, precision="bf16")
 
 
-class _StubEnv:
-    """What PPO.__init__ touches before its first ABI call."""
-
-    def __init__(self):
-        import torch
-        from dronechase_amd import default_config
-        self.cfg, self.N, self.device = default_config("stage03", n_envs=4), 4, torch.device("cpu")
-        self.lidar, self.inertial = torch.zeros(4, 3, 13, 26), torch.zeros(4, 15)
-
-    def reset(self):
-        pass
-
-
 def test_ppo_refuses_the_switch_set_after_the_config_check(lib):
     from dronechase_amd.ppo import PPO, PPOConfig
     cfg = PPOConfig(n_steps=2)
     cfg.fused_forward_bf16 = True
     with pytest.raises(ValueError, match="fused_forward_bf16.*needs fused_forward"):
-        PPO(_StubEnv(), cfg)
+        PPO(StubEnv(), cfg)
 
 
 def test_the_reference_pair_agrees(lib):

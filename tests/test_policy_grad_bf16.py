@@ -25,7 +25,7 @@ import os
 import pytest
 
 from _kinkfree import CLIP, ENT_COEF, SHAPES, VF_COEF, packed_names
-from _policy_cases import _gpu, _shape
+from _policy_cases import StubEnv, _gpu, _shape
 
 DEFAULT, BO, LEARN = SHAPES["default"], SHAPES["BO"], SHAPES["learn"]
 INSTANCES = [(name, c) for name in SHAPES for c in (2, 3)]
@@ -167,28 +167,15 @@ def test_switches_need_their_base(lib):
         FusedPolicy(LidarInertialActionPolicy(), grad_precision="fp16")
 
 
-class _StubEnv:
-    """What PPO.__init__ touches before its first ABI call."""
-
-    def __init__(self):
-        import torch
-        from dronechase_amd import default_config
-        self.cfg, self.N, self.device = default_config("stage03", n_envs=4), 4, torch.device("cpu")
-        self.lidar, self.inertial = torch.zeros(4, 3, 13, 26), torch.zeros(4, 15)
-
-    def reset(self):
-        pass
-
-
 def test_ppo_refuses_the_switch_set_after_the_config_check(lib):
     from dronechase_amd.ppo import PPO, PPOConfig
     cfg = PPOConfig(n_steps=2)
     cfg.fused_update_bf16 = True
     with pytest.raises(ValueError, match="fused_update_bf16.*needs fused_update"):
-        PPO(_StubEnv(), cfg)
+        PPO(StubEnv(), cfg)
     # the wide shapes: the same rule as the fp32 call's
     with pytest.raises(ValueError, match="fused_update_wide"):
-        PPO(_StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_bf16=True, features_dim=BO[0], net_arch=BO[1]))
+        PPO(StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_bf16=True, features_dim=BO[0], net_arch=BO[1]))
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X

@@ -16,7 +16,7 @@ import re
 import numpy as np
 import pytest
 
-from tests._policy_cases import DEFAULT, _compare, _gpu, _kernel, _obs, _policy, _ref, _rollout, _shape, _trained_policy
+from tests._policy_cases import DEFAULT, StubEnv, _compare, _gpu, _kernel, _obs, _policy, _ref, _rollout, _shape, _trained_policy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REL, ABS, KINK = 1e-4, 1e-6, 0.02
@@ -120,19 +120,6 @@ def test_bad_arguments_fail_through_last_error(lib):
         assert msg in err and err.startswith(b"te_policy_ppo_grad_shaped"), (kw, err)
 
 
-class _StubEnv:
-    """What PPO.__init__ touches before its first ABI call, on the CPU."""
-
-    def __init__(self):
-        import torch
-        from dronechase_amd import default_config
-        self.cfg, self.N, self.device = default_config("stage03", n_envs=4), 4, torch.device("cpu")
-        self.lidar, self.inertial = torch.zeros(4, 3, 13, 26), torch.zeros(4, 15)
-
-    def reset(self):
-        pass
-
-
 def test_config_switch(lib):
     from dronechase_amd.ppo import PPO, LidarInertialActionPolicy, PPOConfig
     assert PPOConfig().fused_update_wide is False
@@ -141,17 +128,17 @@ def test_config_switch(lib):
     cfg = PPOConfig(n_steps=2, fused_update=True, fused_update_wide=True)
     cfg.fused_update = False                                  # set after PPOConfig's own check
     with pytest.raises(ValueError, match="fused_update_wide.*needs fused_update"):
-        PPO(_StubEnv(), cfg)
+        PPO(StubEnv(), cfg)
     # past the shape refusal: the next check that fails on a CPU env is the device's
     for extra in (dict(), dict(fused_optimizer=True)):
         with pytest.raises(ValueError, match="needs a GPU device"):
-            PPO(_StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_wide=True, features_dim=512, net_arch=(128, 256, 512), **extra))
+            PPO(StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_wide=True, features_dim=512, net_arch=(128, 256, 512), **extra))
     with pytest.raises(ValueError, match="needs a GPU device"):     # with the default shape the switch changes nothing
-        PPO(_StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_wide=True))
+        PPO(StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_wide=True))
     with pytest.raises(ValueError, match="gradient kernel.*default shape only.*fused_update_wide"):     # without it the refusal names it
-        PPO(_StubEnv(), PPOConfig(n_steps=2, fused_update=True, features_dim=512, net_arch=(128, 256, 512)))
+        PPO(StubEnv(), PPOConfig(n_steps=2, fused_update=True, features_dim=512, net_arch=(128, 256, 512)))
     with pytest.raises(ValueError, match="128, 256, 512"):          # a shape no kernel serves: the list of served ones
-        PPO(_StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_wide=True),
+        PPO(StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_update_wide=True),
             policy=LidarInertialActionPolicy(features_dim=512, net_arch=(128, 256)))
 
 

@@ -13,7 +13,7 @@ import re
 import numpy as np
 import pytest
 
-from tests._policy_cases import DEFAULT, _gpu, _obs, _policy, _shape, _trained_policy
+from tests._policy_cases import DEFAULT, StubEnv, _gpu, _obs, _policy, _shape, _trained_policy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ATOL = RTOL = 1e-4
@@ -203,26 +203,15 @@ def test_load_sb3_policy(lib, tmp_path):
         load_sb3_policy(differs)
 
 
-class _StubEnv:
-    """What PPO.__init__ touches before its first ABI call."""
-
-    def __init__(self):
-        import torch
-        from dronechase_amd import default_config
-        self.cfg, self.N, self.device = default_config("stage03", n_envs=4), 4, torch.device("cpu")
-        self.lidar, self.inertial = torch.zeros(4, 3, 13, 26), torch.zeros(4, 15)
-
-    def reset(self):
-        raise AssertionError("the shape check comes before the env is touched")
-
-
 def test_fused_update_refuses_other_shapes(lib):
     from dronechase_amd.ppo import PPO, LidarInertialActionPolicy, PPOConfig
     assert PPOConfig().features_dim == 256 and PPOConfig().net_arch == (64, 64)
+    env = StubEnv()
     with pytest.raises(ValueError, match="gradient kernel.*default shape only"):
-        PPO(_StubEnv(), PPOConfig(n_steps=2, fused_update=True, net_arch=(128, 256, 512), features_dim=512))
+        PPO(env, PPOConfig(n_steps=2, fused_update=True, net_arch=(128, 256, 512), features_dim=512))
     with pytest.raises(ValueError, match="gradient kernel.*default shape only"):
-        PPO(_StubEnv(), PPOConfig(n_steps=2, fused_update=True, fused_optimizer=True), policy=LidarInertialActionPolicy(features_dim=512, net_arch=LEARN[1]))
+        PPO(env, PPOConfig(n_steps=2, fused_update=True, fused_optimizer=True), policy=LidarInertialActionPolicy(features_dim=512, net_arch=LEARN[1]))
+    assert env.resets == 0      # the shape check comes before the env is touched
 
 
 # ---------------------------------------------------------------------------------------------------------- MI355X

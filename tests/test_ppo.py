@@ -78,24 +78,13 @@ def test_short_training_run_on_device(use_graph):
     env.close()
 
 
-class _StubEnv:
-    """What PPO needs of an environment to build its buffers (no stepping): used where there is no GPU."""
-
-    def __init__(self, n):
-        import torch
-        self.device, self.N = torch.device("cpu"), n
-        self.lidar = torch.ones((n, 3, 13, 26)); self.inertial = torch.zeros((n, 15)); self.cfg = None
-
-    def reset(self):
-        return None
-
-
 def _ppo_rank(rank, world, port, out_dir):
     import os, sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
     import torch.distributed as dist
     from dronechase_amd.ppo import PPO, PPOConfig
+    from tests._policy_cases import StubEnv
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     torch.set_num_threads(2)
 
@@ -111,12 +100,12 @@ def _ppo_rank(rank, world, port, out_dir):
 
     cfg = PPOConfig(n_steps=4, batch_size=32, n_epochs=2, use_graph=False)
     # (1) what a rank would learn on its own data alone (no process group yet)
-    alone = PPO(_StubEnv(16), cfg, seed=5)
+    alone = PPO(StubEnv(None, 16), cfg, seed=5)
     fill(alone, 100 + rank)
     torch.manual_seed(7); alone.update()
     # (2) the data-parallel run: rank-dependent initial weights on purpose, PPO must broadcast rank 0's
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    ppo = PPO(_StubEnv(16), cfg, seed=5 + rank)
+    ppo = PPO(StubEnv(None, 16), cfg, seed=5 + rank)
     assert ppo.distributed
     init = torch.cat([p.detach().flatten() for p in ppo.policy.parameters()]).clone()
     fill(ppo, 100 + rank)

@@ -111,27 +111,15 @@ def test_bad_arguments_fail_through_last_error(lib):
             assert msg in lib.te_last_error(), (kw2, lib.te_last_error())
 
 
-class _CpuEnv:
-    """As much of a BatchedEnv as PPO.__init__ touches before it checks the device of its switches."""
-    N = 4
-
-    def __init__(self):
-        import torch
-        self.device = torch.device("cpu")
-        self.lidar, self.inertial = torch.zeros(self.N, 3, 13, 26), torch.zeros(self.N, 15)
-
-    def reset(self):
-        pass
-
-
 def test_config_switch_needs_a_gpu():
     from dronechase_amd.ppo import PPO, PPOConfig
+    from tests._policy_cases import StubEnv
     assert PPOConfig().fused_advantages is False
     cfg = PPOConfig(n_steps=2, batch_size=8, fused_advantages=True)          # does not need fused_update
     assert cfg.fused_advantages and not cfg.fused_update
     with pytest.raises(ValueError, match="fused_advantages.*needs a GPU"):
-        PPO(_CpuEnv(), cfg)
-    ppo = PPO(_CpuEnv(), PPOConfig(n_steps=2, batch_size=8))                 # the same env is fine with the switch off
+        PPO(StubEnv(None), cfg)
+    ppo = PPO(StubEnv(None), PPOConfig(n_steps=2, batch_size=8))             # the same env is fine with the switch off
     assert not hasattr(ppo, "_adv_stats")
 
 

@@ -10,8 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests._policy_cases import DEFAULT, _shape
-from tests.test_wingman_policy import _clamp, _drone_words, _gpu, _StubEnv
+from tests._policy_cases import DEFAULT, StubEnv, _shape
+from tests.test_wingman_policy import _clamp, _drone_words, _gpu
 
 BO = (512, (128, 256, 512))
 LEARN = (512, (512, 128, 256))
@@ -52,7 +52,7 @@ def test_wingman_bf16_needs_a_driver_stub(lib):
     from dronechase_amd.ppo import PPO, PPOConfig
     for task in ("stage03", "exp05"):
         with pytest.raises(ValueError, match="wingman_bf16"):
-            PPO(_StubEnv(task), PPOConfig(n_steps=2, wingman_bf16=True))
+            PPO(StubEnv(task), PPOConfig(n_steps=2, wingman_bf16=True))
 
 
 # ---------------------------------------------------------------------------------------------------------- GPU

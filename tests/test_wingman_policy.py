@@ -10,6 +10,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests._policy_cases import StubEnv
+
 
 @pytest.fixture(scope="module")
 def lib():
@@ -17,20 +19,6 @@ def lib():
     from dronechase_amd.build import build_library
     build_library()
     return _lib.load()
-
-
-class _StubEnv:
-    """What PPO.__init__ reads of an environment before it fails (no GPU needed)."""
-
-    def __init__(self, task, n=8):
-        import torch
-        from dronechase_amd import default_config
-        self.device, self.N = torch.device("cpu"), n
-        self.lidar = torch.ones((n, 3, 13, 26)); self.inertial = torch.zeros((n, 15))
-        self.cfg = default_config(task, n_envs=n)
-
-    def reset(self):
-        pass
 
 
 # ---------------------------------------------------------------------------------------------------------- no GPU needed
@@ -62,15 +50,15 @@ def test_caller_driven_pursuers(lib):
 def test_ppo_wingman_driver_argument_errors(lib):
     from dronechase_amd.ppo import PPO, LidarInertialActionPolicy, PPOConfig
     with pytest.raises(ValueError, match="PPO drives the agent only"):
-        PPO(_StubEnv("exp05"), PPOConfig(n_steps=2))
+        PPO(StubEnv("exp05"), PPOConfig(n_steps=2))
     with pytest.raises(ValueError, match="needs a GPU device"):
-        PPO(_StubEnv("exp05"), PPOConfig(n_steps=2, wingman_driver="snapshot"))
+        PPO(StubEnv("exp05"), PPOConfig(n_steps=2, wingman_driver="snapshot"))
     with pytest.raises(ValueError, match="no caller-driven pursuer"):
-        PPO(_StubEnv("stage03"), PPOConfig(n_steps=2, wingman_driver="snapshot"))
+        PPO(StubEnv("stage03"), PPOConfig(n_steps=2, wingman_driver="snapshot"))
     with pytest.raises(ValueError, match="wingman_driver must be"):
-        PPO(_StubEnv("exp05"), PPOConfig(n_steps=2, wingman_driver="latest"))
+        PPO(StubEnv("exp05"), PPOConfig(n_steps=2, wingman_driver="latest"))
     with pytest.raises(ValueError, match="pass wingman_policy with wingman_driver='none'"):
-        PPO(_StubEnv("exp05"), PPOConfig(n_steps=2, wingman_driver="snapshot"), wingman_policy=LidarInertialActionPolicy())
+        PPO(StubEnv("exp05"), PPOConfig(n_steps=2, wingman_driver="snapshot"), wingman_policy=LidarInertialActionPolicy())
 
 
 # ---------------------------------------------------------------------------------------------------------- GPU
