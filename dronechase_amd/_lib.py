@@ -22,7 +22,7 @@ EXPORTS = (
     "te_policy_bf16_words", "te_policy_pack_bf16", "te_policy_act_bf16", "te_drive_wingman_bf16",
     "te_policy_bf16_grad_words", "te_policy_pack_bf16_grad", "te_policy_grad_bf16_workspace_bytes", "te_policy_ppo_grad_bf16",
     "te_policy_param_words", "te_policy_act", "te_policy_grad_workspace_bytes", "te_policy_ppo_grad", "te_kernel_plan",
-    "te_policy_opt_state_bytes", "te_policy_adam_step",
+    "te_policy_opt_state_bytes", "te_policy_adam_step", "te_policy_adam_step_bf16", "te_policy_ppo_epoch",
     "te_rollout_gae", "te_adv_stats_workspace_bytes", "te_adv_stats",
     "te_monitor_bytes", "te_monitor_layout", "te_monitor_init", "te_monitor_step", "te_monitor_stats",
 )
@@ -40,6 +40,20 @@ class MonitorOffsets(C.Structure):
 class PolicyShape(C.Structure):
     """te_policy_shape: the policy's LIDAR channels, trunk width and head widths (include/threatengage.h)."""
     _fields_ = [("lidar_channels", C.c_int32), ("features_dim", C.c_int32), ("n_hidden", C.c_int32), ("hidden", C.c_int32 * 4)]
+
+
+class PpoEpochArgs(C.Structure):
+    """te_ppo_epoch_args: everything te_policy_ppo_epoch reads, in the header's order (include/threatengage.h).  The call checks
+    struct_size against its own sizeof."""
+    _fields_ = ([("struct_size", C.c_size_t), ("shape", PolicyShape)]
+                + [(n, C.c_void_p) for n in ("params", "weights_bf16", "weights_bf16_t", "lidar", "inertial", "last_action", "action",
+                                             "old_logp", "adv", "ret", "perm")]
+                + [("n_perm", C.c_int64), ("batch", C.c_int32), ("clip_range", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float),
+                   ("grad", C.c_void_p), ("state", C.c_void_p), ("state_bytes", C.c_size_t),
+                   ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                   ("max_grad_norm", C.c_float), ("grad_scale", C.c_float),
+                   ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("adv_workspace", C.c_void_p), ("adv_workspace_bytes", C.c_size_t),
+                   ("adv_mean_std", C.c_void_p), ("stats", C.c_void_p), ("sums", C.c_void_p)])
 
 
 def load() -> C.CDLL:
@@ -108,6 +122,8 @@ def load() -> C.CDLL:
     L.te_policy_ppo_grad_bf16.argtypes = [vp, vp, vp, shape, i32] + [vp] * 9 + [f32, f32, f32, vp, vp, vp, C.c_size_t, vp]
     L.te_policy_opt_state_bytes.argtypes = [C.c_size_t, C.POINTER(C.c_size_t)]
     L.te_policy_adam_step.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t] + [C.c_double] * 4 + [f32, f32, vp]
+    L.te_policy_adam_step_bf16.argtypes = [vp, vp, vp, C.c_size_t, shape, vp, vp] + [C.c_double] * 4 + [f32, f32, vp]
+    L.te_policy_ppo_epoch.argtypes = [C.POINTER(PpoEpochArgs), vp]
     L.te_rollout_gae.argtypes = [i32, i32] + [vp] * 4 + [C.c_double, C.c_double, vp, vp, vp]
     L.te_adv_stats_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
     L.te_adv_stats.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_size_t, vp]

@@ -1922,53 +1922,83 @@ static int policy_grad_workspace(const char* fn, bool bf16, int shape_id, int32_
   return 0;
 }
 
-static int policy_ppo_grad(const char* fn, const char* size_fn, bool bf16, int shape_id, const float* params, const uint16_t* weights_bf16,
-                           const uint16_t* weights_bf16_t, int32_t lidar_channels, int32_t n, const int64_t* index, const float* lidar,
-                           const float* inertial, const float* last_action, const PolLossInputs& loss, float* grad, float* stats, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-  const std::string who = std::string(fn);
+// One gradient call's arguments but the rows: what te_policy_ppo_epoch keeps from minibatch to minibatch
+struct PolGradCall {
+  bool bf16;
+  int shape_id;
+  const float* params;
+  const uint16_t *weights_bf16, *weights_bf16_t;
+  int32_t lidar_channels;
+  const float *lidar, *inertial, *last_action;
+  PolLossInputs loss;
+  float *grad, *stats;
+  void* workspace;
+  size_t workspace_bytes;
+};
+
+// every check of a gradient call over the n rows `index`, on the host: nothing is launched
+static int policy_ppo_grad_check(const std::string& who, const char* size_fn, const PolGradCall& c, int32_t n, const int64_t* index) {
+  const PolLossInputs& loss = c.loss;
   if (policy_grad_rows_check(who, n)) return 1;
-  if (!params || (bf16 && (!weights_bf16 || !weights_bf16_t)) || !lidar || !inertial || !last_action || !loss.action || !loss.old_logp ||
-      !loss.adv || !loss.ret || !grad || !stats || !workspace)
+  if (!c.params || (c.bf16 && (!c.weights_bf16 || !c.weights_bf16_t)) || !c.lidar || !c.inertial || !c.last_action || !loss.action || !loss.old_logp ||
+      !loss.adv || !loss.ret || !c.grad || !c.stats || !c.workspace)
     return fail(who + ": null argument");
-  if ((uintptr_t)params & 15) return fail(who + ": params must be 16-byte aligned");
-  if (bf16 && ((uintptr_t)weights_bf16 & 15)) return fail(who + ": weights_bf16 must be 16-byte aligned");
-  if (bf16 && ((uintptr_t)weights_bf16_t & 15)) return fail(who + ": weights_bf16_t must be 16-byte aligned");
-  if ((uintptr_t)grad & 15) return fail(who + ": grad must be 16-byte aligned");
-  if ((uintptr_t)lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
-  if ((uintptr_t)workspace & 255) return fail(who + ": workspace must be 256-byte aligned");
+  if ((uintptr_t)c.params & 15) return fail(who + ": params must be 16-byte aligned");
+  if (c.bf16 && ((uintptr_t)c.weights_bf16 & 15)) return fail(who + ": weights_bf16 must be 16-byte aligned");
+  if (c.bf16 && ((uintptr_t)c.weights_bf16_t & 15)) return fail(who + ": weights_bf16_t must be 16-byte aligned");
+  if ((uintptr_t)c.grad & 15) return fail(who + ": grad must be 16-byte aligned");
+  if ((uintptr_t)c.lidar & 7) return fail(who + ": lidar must be 8-byte aligned");
+  if ((uintptr_t)c.workspace & 255) return fail(who + ": workspace must be 256-byte aligned");
   if ((uintptr_t)index & 7) return fail(who + ": index must be 8-byte aligned");
-  for (const void* q : {(const void*)inertial, (const void*)last_action, (const void*)loss.action, (const void*)loss.old_logp,
-                        (const void*)loss.adv, (const void*)loss.ret, (const void*)loss.adv_mean_std, (const void*)stats})
+  for (const void* q : {(const void*)c.inertial, (const void*)c.last_action, (const void*)loss.action, (const void*)loss.old_logp,
+                        (const void*)loss.adv, (const void*)loss.ret, (const void*)loss.adv_mean_std, (const void*)c.stats})
     if ((uintptr_t)q & 3) return fail(who + ": float arrays must be 4-byte aligned");
-  GradTileArgs t; GradTileArgsB tb; GradPlan g;
-  const PolShape shape = pol_shape(shape_id, lidar_channels);
-  const PolicyParams P = policy_params(shape, params);
-  char* const ws = static_cast<char*>(workspace);
-  const size_t need = bf16 ? policy_grad_bf16_layout(shape, n, ws, P, grad, stats, &tb, &g) : policy_grad_layout(shape, n, ws, P, grad, stats, &t, &g);
-  if (workspace_bytes < need)
-    return fail(who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, " + size_fn + " says " + std::to_string(need) + ")");
+  size_t need = 0;
+  if (policy_grad_workspace(who.c_str(), c.bf16, c.shape_id, c.lidar_channels, n, &need)) return 1;
+  if (c.workspace_bytes < need)
+    return fail(who + ": workspace too small (" + std::to_string(c.workspace_bytes) + " bytes, " + size_fn + " says " + std::to_string(need) + ")");
   if (!std::isfinite(loss.clip_range) || loss.clip_range < 0.f) return fail(who + ": clip_range must be finite and >= 0");
-  const PolicyIn in{lidar, inertial, last_action, index, n};
+  return 0;
+}
+
+// the three launches of a checked gradient call
+static int policy_ppo_grad_launch(const PolGradCall& c, int32_t n, const int64_t* index, void* stream) {
+  GradTileArgs t; GradTileArgsB tb; GradPlan g;
+  const PolShape shape = pol_shape(c.shape_id, c.lidar_channels);
+  const PolicyParams P = policy_params(shape, c.params);
+  char* const ws = static_cast<char*>(c.workspace);
+  if (c.bf16) policy_grad_bf16_layout(shape, n, ws, P, c.grad, c.stats, &tb, &g);
+  else policy_grad_layout(shape, n, ws, P, c.grad, c.stats, &t, &g);
+  const PolicyIn in{c.lidar, c.inertial, c.last_action, index, n};
   const hipStream_t s = (hipStream_t)stream;
   // the tile grid covers the workspace's Bp rows (n rounded up to 32), not n: a 16-row shape's padding tile writes its rows too, and a
   // padding row writes its zeros like any other
   const int Bp = g.L[POL_L_MU].R;
-  if (bf16) {
-    policy_loss_inputs(tb, loss, n);
-    if (policy_launch(kPolicyGradBf16Kernels[shape_id][lidar_channels - 2], pol_geom(pol_grad_lds_plan_bf16(shape)), Bp, stream, P,
-                      policy_weights(shape, weights_bf16), policy_weights_t(shape, weights_bf16_t), in, tb))
+  if (c.bf16) {
+    policy_loss_inputs(tb, c.loss, n);
+    if (policy_launch(kPolicyGradBf16Kernels[c.shape_id][c.lidar_channels - 2], pol_geom(pol_grad_lds_plan_bf16(shape)), Bp, stream, P,
+                      policy_weights(shape, c.weights_bf16), policy_weights_t(shape, c.weights_bf16_t), in, tb))
       return 1;
   } else {
-    policy_loss_inputs(t, loss, n);
-    if (policy_launch(kPolicyGradKernels[shape_id][lidar_channels - 2], pol_geom(pol_lds_plan(shape)), Bp, stream, P, in, t)) return 1;
+    policy_loss_inputs(t, c.loss, n);
+    if (policy_launch(kPolicyGradKernels[c.shape_id][c.lidar_channels - 2], pol_geom(pol_lds_plan(shape)), Bp, stream, P, in, t)) return 1;
   }
-  void (*const wgrad)(GradPlan) = bf16 ? policy_wgrad_bf16_kernel : policy_wgrad_kernel;
+  void (*const wgrad)(GradPlan) = c.bf16 ? policy_wgrad_bf16_kernel : policy_wgrad_kernel;
   hipLaunchKernelGGL(wgrad, dim3((unsigned)g.wgs), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(policy_grad_combine_kernel, dim3((unsigned)((g.words + 255) / 256)), dim3(256), 0, s, g);
   TE_HIP(hipGetLastError());
   return 0;
+}
+
+static int policy_ppo_grad(const char* fn, const char* size_fn, bool bf16, int shape_id, const float* params, const uint16_t* weights_bf16,
+                           const uint16_t* weights_bf16_t, int32_t lidar_channels, int32_t n, const int64_t* index, const float* lidar,
+                           const float* inertial, const float* last_action, const PolLossInputs& loss, float* grad, float* stats, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  const PolGradCall c{bf16, shape_id, params, weights_bf16, weights_bf16_t, lidar_channels, lidar, inertial, last_action, loss, grad, stats,
+                      workspace, workspace_bytes};
+  if (policy_ppo_grad_check(fn, size_fn, c, n, index)) return 1;
+  return policy_ppo_grad_launch(c, n, index, stream);
 }
 
 __attribute__((visibility("default"))) int te_policy_grad_workspace_bytes(int32_t lidar_channels, int32_t n, size_t* out_bytes) {
@@ -2057,33 +2087,90 @@ __attribute__((visibility("default"))) int te_policy_opt_state_bytes(size_t word
   return 0;
 }
 
+// One step's arguments: what te_policy_adam_step, te_policy_adam_step_bf16 and te_policy_ppo_epoch check and launch alike
+struct AdamCall {
+  float* params;
+  const float* grad;
+  void* state;
+  size_t state_bytes, words;
+  double lr, beta1, beta2, eps;
+  float max_grad_norm, grad_scale;
+};
+
+static int policy_adam_check(const std::string& who, const AdamCall& c) {
+  if (!c.params || !c.grad || !c.state) return fail(who + ": null argument");
+  if ((uintptr_t)c.params & 15) return fail(who + ": params must be 16-byte aligned");
+  if ((uintptr_t)c.grad & 15) return fail(who + ": grad must be 16-byte aligned");
+  if ((uintptr_t)c.state & 15) return fail(who + ": state must be 16-byte aligned");
+  if (policy_opt_words_check(who.c_str(), c.words)) return 1;
+  const OptLayout o = opt_layout(c.words);
+  if (c.state_bytes < o.bytes)
+    return fail(who + ": state too small (" + std::to_string(c.state_bytes) + " bytes, te_policy_opt_state_bytes says " +
+                std::to_string(o.bytes) + ")");
+  if (!(c.lr >= 0.0) || !std::isfinite(c.lr)) return fail(who + ": lr must be finite and >= 0");
+  if (!(c.beta1 >= 0.0 && c.beta1 < 1.0)) return fail(who + ": beta1 must be in [0, 1)");
+  if (!(c.beta2 >= 0.0 && c.beta2 < 1.0)) return fail(who + ": beta2 must be in [0, 1)");
+  if (!(c.eps > 0.0) || !std::isfinite(c.eps)) return fail(who + ": eps must be finite and > 0");
+  if (!(c.max_grad_norm > 0.f)) return fail(who + ": max_grad_norm must be > 0 (INFINITY: no clipping)");
+  if (!std::isfinite(c.grad_scale)) return fail(who + ": grad_scale must be finite");
+  return 0;
+}
+
+// the two launches of a checked step; repack: the bf16 destinations of te_policy_adam_step_bf16, or NULL
+static int policy_adam_launch(const AdamCall& c, const OptRepack* repack, void* stream) {
+  const AdamArgs a{c.lr, c.beta1, c.beta2, (float)c.beta1, (float)c.beta2, (float)(1.0 - c.beta1), (float)(1.0 - c.beta2), (float)c.eps,
+                   c.max_grad_norm, c.grad_scale};
+  const OptView view = opt_view(c.state, c.words);
+  const dim3 grid((unsigned)opt_layout(c.words).n_partials);
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(policy_gradnorm_kernel, grid, dim3(kOptThreads), 0, s, view, c.grad, c.grad_scale);
+  TE_HIP(hipGetLastError());
+  if (repack) hipLaunchKernelGGL(policy_adam_kernel<true>, grid, dim3(kOptThreads), 0, s, view, c.params, c.grad, a, *repack);
+  else hipLaunchKernelGGL(policy_adam_kernel<false>, grid, dim3(kOptThreads), 0, s, view, c.params, c.grad, a, OptNoRepack{});
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
 __attribute__((visibility("default"))) int te_policy_adam_step(float* params, const float* grad, void* state, size_t state_bytes, size_t words,
                                                                double lr, double beta1, double beta2, double eps, float max_grad_norm,
                                                                float grad_scale, void* stream) {
-  if (!params || !grad || !state) return fail("te_policy_adam_step: null argument");
-  if ((uintptr_t)params & 15) return fail("te_policy_adam_step: params must be 16-byte aligned");
-  if ((uintptr_t)grad & 15) return fail("te_policy_adam_step: grad must be 16-byte aligned");
-  if ((uintptr_t)state & 15) return fail("te_policy_adam_step: state must be 16-byte aligned");
-  if (policy_opt_words_check("te_policy_adam_step", words)) return 1;
-  const OptLayout o = opt_layout(words);
-  if (state_bytes < o.bytes)
-    return fail("te_policy_adam_step: state too small (" + std::to_string(state_bytes) + " bytes, te_policy_opt_state_bytes says " +
-                std::to_string(o.bytes) + ")");
-  if (!(lr >= 0.0) || !std::isfinite(lr)) return fail("te_policy_adam_step: lr must be finite and >= 0");
-  if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail("te_policy_adam_step: beta1 must be in [0, 1)");
-  if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail("te_policy_adam_step: beta2 must be in [0, 1)");
-  if (!(eps > 0.0) || !std::isfinite(eps)) return fail("te_policy_adam_step: eps must be finite and > 0");
-  if (!(max_grad_norm > 0.f)) return fail("te_policy_adam_step: max_grad_norm must be > 0 (INFINITY: no clipping)");
-  if (!std::isfinite(grad_scale)) return fail("te_policy_adam_step: grad_scale must be finite");
-  const AdamArgs a{lr, beta1, beta2, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, max_grad_norm, grad_scale};
-  const OptView view = opt_view(state, words);
-  const dim3 grid((unsigned)o.n_partials);
-  const hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(policy_gradnorm_kernel, grid, dim3(kOptThreads), 0, s, view, grad, grad_scale);
-  TE_HIP(hipGetLastError());
-  hipLaunchKernelGGL(policy_adam_kernel, grid, dim3(kOptThreads), 0, s, view, params, grad, a);
-  TE_HIP(hipGetLastError());
+  const AdamCall c{params, grad, state, state_bytes, words, lr, beta1, beta2, eps, max_grad_norm, grad_scale};
+  if (policy_adam_check("te_policy_adam_step", c)) return 1;
+  return policy_adam_launch(c, nullptr, stream);
+}
+
+// The bf16 destinations of a shape's stepped words, from the pack kernels' own plans: range l is layer l's weight
+static OptRepack policy_repack_plan(PolShape shape, uint16_t* weights_bf16, uint16_t* weights_bf16_t) {
+  static_assert(kPolBMfmaLayers <= kOptRepackRanges, "one range per layer of the bf16 buffer");
+  const PolPackPlan p = policy_pack_plan(shape);
+  const PolPackTPlan t = policy_pack_t_plan(shape);
+  OptRepack r{};
+  for (int l = 0; l < kPolBMfmaLayers; ++l)
+    r.r[l] = {p.l[l].src, p.l[l].src + t.l[l].N * p.l[l].K, p.l[l].K, p.l[l].Kp, p.l[l].dst, t.l[l].Np, pol_needs_dx(l) ? t.l[l].dst : -1};
+  r.out = reinterpret_cast<__bf16*>(weights_bf16);
+  r.out_t = reinterpret_cast<__bf16*>(weights_bf16_t);
+  return r;
+}
+
+// te_policy_adam_step_bf16's own checks, behind policy_adam_check
+static int policy_repack_check(const std::string& who, const uint16_t* weights_bf16, const uint16_t* weights_bf16_t) {
+  if (!weights_bf16) return fail(who + ": weights_bf16 is required");
+  if ((uintptr_t)weights_bf16 & 15) return fail(who + ": weights_bf16 must be 16-byte aligned");
+  if ((uintptr_t)weights_bf16_t & 15) return fail(who + ": weights_bf16_t must be 16-byte aligned");
   return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_adam_step_bf16(float* params, const float* grad, void* state, size_t state_bytes,
+                                                                    const te_policy_shape* shape, uint16_t* weights_bf16,
+                                                                    uint16_t* weights_bf16_t, double lr, double beta1, double beta2, double eps,
+                                                                    float max_grad_norm, float grad_scale, void* stream) {
+  const int id = policy_shape_id(shape, "te_policy_adam_step_bf16");
+  if (id < 0) return 1;
+  const PolShape s = pol_shape(id, shape->lidar_channels);
+  const AdamCall c{params, grad, state, state_bytes, (size_t)policy_layout(s).words, lr, beta1, beta2, eps, max_grad_norm, grad_scale};
+  if (policy_adam_check("te_policy_adam_step_bf16", c) || policy_repack_check("te_policy_adam_step_bf16", weights_bf16, weights_bf16_t)) return 1;
+  const OptRepack repack = policy_repack_plan(s, weights_bf16, weights_bf16_t);
+  return policy_adam_launch(c, &repack, stream);
 }
 
 // ---- advantage estimation (te_rollout.hpp): every check is on the host, before any launch
@@ -2130,17 +2217,22 @@ __attribute__((visibility("default"))) int te_adv_stats_workspace_bytes(int64_t 
   return 0;
 }
 
-__attribute__((visibility("default"))) int te_adv_stats(const float* x, const int64_t* index, int64_t n, float* out_mean_std, void* workspace,
-                                                        size_t workspace_bytes, void* stream) {
-  if (!x || !out_mean_std || !workspace) return fail("te_adv_stats: null argument");
-  if (adv_stats_n_check("te_adv_stats", n)) return 1;
-  if (((uintptr_t)x | (uintptr_t)out_mean_std) & 3) return fail("te_adv_stats: float arrays must be 4-byte aligned");
-  if ((uintptr_t)index & 7) return fail("te_adv_stats: index must be 8-byte aligned");
-  if ((uintptr_t)workspace & 7) return fail("te_adv_stats: workspace must be 8-byte aligned");
+static int adv_stats_check(const std::string& who, const float* x, const int64_t* index, int64_t n, const float* out_mean_std,
+                           const void* workspace, size_t workspace_bytes) {
+  if (!x || !out_mean_std || !workspace) return fail(who + ": null argument");
+  if (adv_stats_n_check(who.c_str(), n)) return 1;
+  if (((uintptr_t)x | (uintptr_t)out_mean_std) & 3) return fail(who + ": float arrays must be 4-byte aligned");
+  if ((uintptr_t)index & 7) return fail(who + ": index must be 8-byte aligned");
+  if ((uintptr_t)workspace & 7) return fail(who + ": workspace must be 8-byte aligned");
   const size_t need = stat_workspace_bytes(n);
   if (workspace_bytes < need)
-    return fail("te_adv_stats: workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_adv_stats_workspace_bytes says " +
+    return fail(who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_adv_stats_workspace_bytes says " +
                 std::to_string(need) + ")");
+  return 0;
+}
+
+// the two launches of a checked statistics call
+static int adv_stats_launch(const float* x, const int64_t* index, int64_t n, float* out_mean_std, void* workspace, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   const size_t slices = stat_slices(n);
   double* partials = static_cast<double*>(workspace);
@@ -2149,6 +2241,83 @@ __attribute__((visibility("default"))) int te_adv_stats(const float* x, const in
   TE_HIP(hipGetLastError());
   hipLaunchKernelGGL(adv_stats_final_kernel, dim3(1), dim3(kStatThreads), 0, s, x, index, n, (const double*)partials, (int64_t)slices, out_mean_std);
   TE_HIP(hipGetLastError());
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_adv_stats(const float* x, const int64_t* index, int64_t n, float* out_mean_std, void* workspace,
+                                                        size_t workspace_bytes, void* stream) {
+  if (adv_stats_check("te_adv_stats", x, index, n, out_mean_std, workspace, workspace_bytes)) return 1;
+  return adv_stats_launch(x, index, n, out_mean_std, workspace, stream);
+}
+
+// ---- te_policy_ppo_epoch: every minibatch of an epoch, the four calls above enqueued back to back by one host loop
+// The rows of minibatch k of an epoch over n_perm rows in minibatches of `batch`: perm[s .. s + b)
+struct EpochSlice { int64_t s; int32_t b; };
+static EpochSlice epoch_slice(int64_t n_perm, int32_t batch, int64_t k) {
+  const int64_t s = k * (int64_t)batch, left = n_perm - s;
+  return {s, (int32_t)(left < (int64_t)batch ? left : (int64_t)batch)};
+}
+
+// every check of te_policy_ppo_epoch, on the host: nothing is launched.  out: the calls the loop repeats
+static int policy_ppo_epoch_check(const te_ppo_epoch_args* a, PolGradCall* grad_call, AdamCall* adam_call, bool* bf16) {
+  const std::string who = "te_policy_ppo_epoch";
+  if (!a) return fail(who + ": null argument");
+  if (a->struct_size != sizeof(te_ppo_epoch_args))
+    return fail(who + ": args->struct_size is " + std::to_string(a->struct_size) + ", sizeof(te_ppo_epoch_args) is " +
+                std::to_string(sizeof(te_ppo_epoch_args)));
+  const int id = policy_shape_id(&a->shape, who.c_str());
+  if (id < 0) return 1;
+  if (a->batch < 1) return fail(who + ": batch must be >= 1");
+  if (a->n_perm < 1) return fail(who + ": n_perm must be >= 1");
+  if (a->n_perm > ((int64_t)1 << 40)) return fail(who + ": n_perm must be at most 2^40");      // te_adv_stats's own limit; perm + s stays a pointer
+  if (!a->perm) return fail(who + ": perm is required");
+  if ((uintptr_t)a->perm & 7) return fail(who + ": perm must be 8-byte aligned");
+  if (!a->weights_bf16 != !a->weights_bf16_t)
+    return fail(who + ": weights_bf16 and weights_bf16_t go together: both NULL (the fp32 gradient and te_policy_adam_step) or both given "
+                      "(te_policy_ppo_grad_bf16 and te_policy_adam_step_bf16)");
+  *bf16 = a->weights_bf16 != nullptr;
+  if (!a->adv_mean_std || !a->stats || !a->sums) return fail(who + ": adv_mean_std, stats and sums are required");
+  if ((uintptr_t)a->sums & 3) return fail(who + ": sums must be 4-byte aligned");
+  const PolShape shape = pol_shape(id, a->shape.lidar_channels);
+  *grad_call = PolGradCall{*bf16, id, a->params, a->weights_bf16, a->weights_bf16_t, a->shape.lidar_channels, a->lidar, a->inertial, a->last_action,
+                           {a->action, a->old_logp, a->adv, a->ret, a->adv_mean_std, a->clip_range, a->vf_coef, a->ent_coef}, a->grad, a->stats,
+                           a->workspace, a->workspace_bytes};
+  *adam_call = AdamCall{a->params, a->grad, a->state, a->state_bytes, (size_t)policy_layout(shape).words, a->lr, a->beta1, a->beta2, a->eps,
+                        a->max_grad_norm, a->grad_scale};
+  // the two sizes a minibatch has: the first one's and the last one's (the tail; the same when batch divides n_perm)
+  const int64_t last = (a->n_perm - 1) / a->batch;
+  for (const int64_t k : {(int64_t)0, last}) {
+    const EpochSlice m = epoch_slice(a->n_perm, a->batch, k);
+    if (adv_stats_check(who, a->adv, a->perm + m.s, m.b, a->adv_mean_std, a->adv_workspace, a->adv_workspace_bytes)) return 1;
+    if (policy_ppo_grad_check(who, *bf16 ? "te_policy_grad_bf16_workspace_bytes" : "te_policy_grad_workspace_bytes_shaped", *grad_call, m.b,
+                              a->perm + m.s))
+      return 1;
+  }
+  if (policy_adam_check(who, *adam_call)) return 1;
+  if (*bf16 && policy_repack_check(who, a->weights_bf16, a->weights_bf16_t)) return 1;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_policy_ppo_epoch(const te_ppo_epoch_args* args, void* stream) {
+  PolGradCall g; AdamCall o; bool bf16;
+  if (policy_ppo_epoch_check(args, &g, &o, &bf16)) return 1;
+  const PolShape shape = pol_shape(g.shape_id, g.lidar_channels);
+  // the tile kernel's LDS opt-in is the one step of a launch that is not a launch: taken now, so a refusal still comes before the first one
+  if (bf16 ? policy_opt_in(reinterpret_cast<const void*>(kPolicyGradBf16Kernels[g.shape_id][g.lidar_channels - 2]), pol_grad_lds_plan_bf16(shape).bytes)
+           : policy_opt_in(reinterpret_cast<const void*>(kPolicyGradKernels[g.shape_id][g.lidar_channels - 2]), pol_lds_plan(shape).words * 4))
+    return 1;
+  const OptRepack repack = policy_repack_plan(shape, args->weights_bf16, args->weights_bf16_t);
+  const float* norm = opt_view(args->state, o.words).norm;
+  const int64_t n_batches = (args->n_perm - 1) / args->batch + 1;
+  for (int64_t k = 0; k < n_batches; ++k) {
+    const EpochSlice m = epoch_slice(args->n_perm, args->batch, k);
+    const int64_t* index = args->perm + m.s;
+    if (adv_stats_launch(args->adv, index, m.b, args->adv_mean_std, args->adv_workspace, stream)) return 1;
+    if (policy_ppo_grad_launch(g, m.b, index, stream)) return 1;
+    if (policy_adam_launch(o, bf16 ? &repack : nullptr, stream)) return 1;
+    hipLaunchKernelGGL(policy_epoch_sums_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, args->sums, (const float*)args->stats, norm);
+    TE_HIP(hipGetLastError());
+  }
   return 0;
 }
 

@@ -14,10 +14,17 @@
 // No atomics at all: every sum has a fixed order, so a step depends on its inputs only.  The kernel boundary orders the partials and
 // the step counter between the two launches.  Traffic of a step: g twice, p, m, v read and written = 28 bytes per word (6.6 MB for
 // the policy's 235 049 words, L2-resident): the step is bound by its two launches.
+//
+// policy_adam_kernel<true> (te_policy_adam_step_bf16) is the same step with one addition: the thread that has just computed word w of a
+// weight also stores its bf16 rounding (nearest-even, the `(__bf16)` conversion of the pack kernels) where te_policy_pack_bf16 and
+// te_policy_pack_bf16_grad would put it, so the rounded copies are current when the step ends and no repack launch follows.  This header
+// still knows no layer: the word ranges and the destinations' strides arrive as a table, OptRepack, which the host derives from the pack
+// kernels' own plans.  Pad columns are not words of `params`: nobody writes them here, they keep the zeros of the first pack.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 namespace te {
 
@@ -61,6 +68,29 @@ struct AdamArgs {                        // the call's scalars, by value: a capt
   double lr, beta1, beta2;
   float b1, b2, one_minus_b1, one_minus_b2, eps, max_norm, scale;
 };
+
+// Where the bf16 roundings of the stepped words go.  Range r covers the words [src, end) of one weight [N][K], row-major; word
+// src + n K + k goes to out[dst + n Kp + k] and, when the range has a transposed block (dst_t >= 0) and out_t is given, to
+// out_t[dst_t + k Np + n].  Words outside every range (biases, mu, value, log_std) have no bf16 copy; an unused range is empty.
+// A kernel argument by value: index `r` with compile-time constants only.
+constexpr int kOptRepackRanges = 16;
+struct OptRepack {
+  struct { int src, end, K, Kp, dst, Np, dst_t; } r[kOptRepackRanges];
+  __bf16 *out, *out_t;
+};
+struct OptNoRepack {};                   // policy_adam_kernel<false>'s: te_policy_adam_step
+
+__device__ inline void opt_repack_word(const OptRepack& t, int w, float p) {
+  int src = 0, K = 1, Kp = 0, dst = -1, Np = 0, dst_t = -1;
+#pragma unroll
+  for (int i = 0; i < kOptRepackRanges; ++i)
+    if (w >= t.r[i].src && w < t.r[i].end) { src = t.r[i].src; K = t.r[i].K; Kp = t.r[i].Kp; dst = t.r[i].dst; Np = t.r[i].Np; dst_t = t.r[i].dst_t; }
+  if (dst < 0) return;
+  const int e = w - src, n = e / K, k = e - n * K;
+  const __bf16 h = (__bf16)p;
+  t.out[dst + n * Kp + k] = h;
+  if (t.out_t && dst_t >= 0) t.out_t[dst_t + k * Np + n] = h;
+}
 
 template <typename T>
 __device__ inline T opt_block_sum(T x, T* wave_sums) {   // a fixed tree over the 256 threads; every thread returns the total
@@ -113,8 +143,9 @@ __device__ inline void opt_adam(float g, float& p, float& m, float& v, const Ada
   p -= step_size * (m / (sqrtf(v) / bc2_sqrt + a.eps));
 }
 
+template <bool REPACK>
 __global__ __launch_bounds__(kOptThreads) void policy_adam_kernel(OptView o, float* __restrict__ params, const float* __restrict__ grad,
-                                                                  AdamArgs a) {
+                                                                  AdamArgs a, std::conditional_t<REPACK, OptRepack, OptNoRepack> repack) {
   __shared__ double wave_sums[kOptThreads / 64];
   __shared__ float bias[2];              // lr / (1 - beta1^t), sqrt(1 - beta2^t)
   double part = 0.0;
@@ -143,9 +174,26 @@ __global__ __launch_bounds__(kOptThreads) void policy_adam_kernel(OptView o, flo
     opt_adam(gq.z, pq.z, mq.z, vq.z, a, coef, step_size, bc2_sqrt);
     opt_adam(gq.w, pq.w, mq.w, vq.w, a, coef, step_size, bc2_sqrt);
     reinterpret_cast<float4*>(p)[i] = pq; reinterpret_cast<float4*>(m)[i] = mq; reinterpret_cast<float4*>(v)[i] = vq;
+    if constexpr (REPACK) {              // a float4 may straddle two rows or two layers (K = 15, K = 4): word by word
+      const int w = (int)base + 4 * i;
+      opt_repack_word(repack, w, pq.x); opt_repack_word(repack, w + 1, pq.y);
+      opt_repack_word(repack, w + 2, pq.z); opt_repack_word(repack, w + 3, pq.w);
+    }
   }
   const int tail = (n4 << 2) + (int)threadIdx.x;
-  if (tail < n) opt_adam(g[tail], p[tail], m[tail], v[tail], a, coef, step_size, bc2_sqrt);
+  if (tail < n) {
+    opt_adam(g[tail], p[tail], m[tail], v[tail], a, coef, step_size, bc2_sqrt);
+    if constexpr (REPACK) opt_repack_word(repack, (int)base + tail, p[tail]);
+  }
+}
+
+// te_policy_ppo_epoch's log, behind every minibatch's step: the gradient call's four statistics and the step's norm before clipping
+// are added to the caller's running sums.  One thread, five fp32 adds in index order: the adds PPO.update() makes from Python.
+__global__ void policy_epoch_sums_kernel(float* sums, const float* stats, const float* norm) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) sums[i] += stats[i];
+  sums[4] += *norm;
 }
 
 }  // namespace te

@@ -338,20 +338,67 @@ class FusedPolicy:
         require_index("FusedPolicy.ppo_grad", index, self.device)
         if b == 0:
             raise ValueError("FusedPolicy.ppo_grad: the minibatch is empty")
-        need = C.c_size_t()
-        _lib.call(self.grad_ws_entry, C.byref(self.shape), b, C.byref(need))
-        ws = getattr(self, "_grad_ws", None)
-        if ws is None or ws.numel() < need.value:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FusedPolicy.ppo_grad: the workspace must grow, which a capturing stream does not allow; "
-                                   "call once with this minibatch size before capture")
-            self._grad_ws = None           # free the old workspace before the larger one is allocated
-            ws = self._grad_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
+        ws = self._grad_workspace("FusedPolicy.ppo_grad", b)
         entry, weights = self.grad_entry
         _lib.call_on(self.device, entry, *(w.data_ptr() for w in weights), C.byref(self.shape), b, _ptr(index), lidar.data_ptr(),
                      inertial.data_ptr(), last_action.data_ptr(), action.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), ret.data_ptr(),
                      _ptr(adv_mean_std), float(clip), float(vf_coef), float(ent_coef), grad_out.data_ptr(), stats_out.data_ptr(),
                      ws.data_ptr(), ws.numel())
+
+    def _grad_workspace(self, who: str, rows: int) -> torch.Tensor:
+        """The gradient workspace for minibatches of up to `rows` rows: owned here, grown on demand, never under capture."""
+        need = C.c_size_t()
+        _lib.call(self.grad_ws_entry, C.byref(self.shape), rows, C.byref(need))
+        ws = getattr(self, "_grad_ws", None)
+        if ws is None or ws.numel() < need.value:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{who}: the workspace must grow, which a capturing stream does not allow; "
+                                   "call once with this minibatch size before capture")
+            self._grad_ws = None           # free the old workspace before the larger one is allocated
+            ws = self._grad_ws = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def ppo_epoch(self, obs: Dict[str, torch.Tensor], perm: torch.Tensor, batch: int, action: torch.Tensor, old_logp: torch.Tensor,
+                  adv: torch.Tensor, ret: torch.Tensor, clip: float, vf_coef: float, ent_coef: float, grad_out: torch.Tensor,
+                  opt: "PackedAdam", max_grad_norm: float, adv_workspace: torch.Tensor, adv_mean_std: torch.Tensor,
+                  stats: torch.Tensor, sums: torch.Tensor, grad_scale: float = 1.0) -> None:
+        """One epoch of PPO's update by ONE te_policy_ppo_epoch call: for every minibatch perm[s:s + batch] of the int64 row numbers
+        `perm` (the last one may be shorter) the advantage statistics (adv_stats into adv_mean_std [2]), the gradient (ppo_grad's call
+        into grad_out and stats [4]), `opt`'s clipped Adam step on this object's packed buffer, and sums [5] += (pg, vl, ent, clip_frac,
+        the gradient's norm before clipping), enqueued back to back on PyTorch's current stream with no return to Python in between.
+        Bitwise the same calls made one by one.  grad_precision="bf16": the bf16 gradient, and the step keeps weights_bf16 and
+        weights_bf16_t current (te_policy_adam_step_bf16), so no refresh() is needed between the minibatches; they must be current
+        when the call starts.  sums is added to, not cleared.  The gradient workspace is owned here, as ppo_grad's is;
+        adv_workspace comes from adv_stats_workspace(n) with n >= batch."""
+        who = "FusedPolicy.ppo_epoch"
+        lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
+        m = lidar.shape[0]
+        for name, t, shape in (("lidar", lidar, (m, self.lidar_channels, 13, 26)), ("inertial_data", inertial, (m, 15)),
+                               ("last_action", last_action, (m, 4)), ("action", action, (m, 4)), ("old_logp", old_logp, (m,)),
+                               ("adv", adv, (m,)), ("ret", ret, (m,)), ("grad_out", grad_out, (self.params.numel(),)),
+                               ("adv_mean_std", adv_mean_std, (2,)), ("stats", stats, (4,)), ("sums", sums, (5,))):
+            require_f32(who, name, t, shape, self.device)
+        if perm is None or perm.numel() == 0:
+            raise ValueError(f"{who}: perm is required and must not be empty")
+        require_index(who, perm, self.device)
+        if opt.fused_policy is not self:
+            raise ValueError(f"{who}: opt must be the PackedAdam of this FusedPolicy")
+        if adv_workspace.dtype != torch.uint8 or adv_workspace.device != self.device or not adv_workspace.is_contiguous():
+            raise ValueError(f"{who}: adv_workspace must be a contiguous uint8 tensor on {self.device} (adv_stats_workspace)")
+        batch = int(batch)
+        ws = self._grad_workspace(who, max(1, min(batch, perm.numel())))
+        bf16 = self.weights_bf16_t is not None      # grad_precision == "bf16": the object owns both rounded copies
+        a = _lib.PpoEpochArgs(
+            struct_size=C.sizeof(_lib.PpoEpochArgs), shape=self.shape, params=self.params.data_ptr(),
+            weights_bf16=self.weights_bf16.data_ptr() if bf16 else None, weights_bf16_t=self.weights_bf16_t.data_ptr() if bf16 else None,
+            lidar=lidar.data_ptr(), inertial=inertial.data_ptr(), last_action=last_action.data_ptr(), action=action.data_ptr(),
+            old_logp=old_logp.data_ptr(), adv=adv.data_ptr(), ret=ret.data_ptr(), perm=perm.data_ptr(), n_perm=perm.numel(), batch=batch,
+            clip_range=float(clip), vf_coef=float(vf_coef), ent_coef=float(ent_coef), grad=grad_out.data_ptr(),
+            state=opt.state.data_ptr(), state_bytes=opt.state.numel() * 4, lr=opt.lr, beta1=opt.betas[0], beta2=opt.betas[1], eps=opt.eps,
+            max_grad_norm=float(max_grad_norm), grad_scale=float(grad_scale), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+            adv_workspace=adv_workspace.data_ptr(), adv_workspace_bytes=adv_workspace.numel(), adv_mean_std=adv_mean_std.data_ptr(),
+            stats=stats.data_ptr(), sums=sums.data_ptr())
+        _lib.call_on(self.device, "te_policy_ppo_epoch", C.byref(a))
 
     def _call(self, obs, eps, outs):
         lidar, inertial, last_action = obs["lidar"], obs["inertial_data"], obs["last_action"]
@@ -402,13 +449,24 @@ class PackedAdam:
         self.grad_norm, self.clip_coef = self.state[1:2], self.state[2:3]
         self.exp_avg, self.exp_avg_sq = self.state[16:16 + self.words], self.state[16 + a:16 + a + self.words]
 
-    def step(self, grad: torch.Tensor, max_grad_norm: float, grad_scale: float = 1.0) -> None:
+    def step(self, grad: torch.Tensor, max_grad_norm: float, grad_scale: float = 1.0, repack: bool = False) -> None:
         """One clipped Adam step on `grad` [words] (the packed order, 16-byte aligned); max_grad_norm = inf does not clip;
-        grad_scale multiplies the gradient before the norm and the update (1 / world_size after an all-reduce)."""
+        grad_scale multiplies the gradient before the norm and the update (1 / world_size after an all-reduce).
+        repack=True: te_policy_adam_step_bf16, the same step (params and state bitwise the same) that also leaves the FusedPolicy's
+        weights_bf16 and, when it owns one, weights_bf16_t current, so no refresh() has to follow; a ValueError when the FusedPolicy
+        owns no bf16 buffer."""
         f = self.fused_policy
+        if repack and f.weights_bf16 is None:
+            raise ValueError("PackedAdam.step: repack=True keeps the FusedPolicy's bf16 weights current, and this one owns none "
+                             "(FusedPolicy(precision='bf16') or grad_precision='bf16')")
         require_f32("PackedAdam.step", "grad", grad, (self.words,), f.device)
+        scalars = (self.lr, self.betas[0], self.betas[1], self.eps, float(max_grad_norm), float(grad_scale))
+        if repack:
+            _lib.call_on(f.device, "te_policy_adam_step_bf16", f.params.data_ptr(), grad.data_ptr(), self.state.data_ptr(),
+                         self.state.numel() * 4, C.byref(f.shape), f.weights_bf16.data_ptr(), _ptr(f.weights_bf16_t), *scalars)
+            return
         _lib.call_on(f.device, "te_policy_adam_step", f.params.data_ptr(), grad.data_ptr(), self.state.data_ptr(), self.state.numel() * 4,
-                     self.words, self.lr, self.betas[0], self.betas[1], self.eps, float(max_grad_norm), float(grad_scale))
+                     self.words, *scalars)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         return {"state": self.state.clone()}
@@ -583,12 +641,29 @@ class PPOConfig:
     # no longer lose to fast_learner (2.5 x and 2.1 x faster).  At 8 192 rows 0.69 / 0.74 / 0.77 ms against fast_learner's 4.08 / 3.78 / 3.74 ms.
     # Off by default
     fused_update_bf16: bool = False
+    # update(): every minibatch of an epoch enqueued by ONE ABI call (te_policy_ppo_epoch, FusedPolicy.ppo_epoch): per epoch one
+    # torch.randperm and one call whose host loop, in C, launches the advantage statistics, the gradient, the Adam step and the log's
+    # running sums of every minibatch back to back, instead of five ctypes calls, a slice and two tensor adds per minibatch from Python.
+    # Needs fused_update, fused_optimizer and fused_advantages (the three calls it chains) and a GPU; composes with fused_update_wide and
+    # fused_update_bf16, where the step itself keeps the bf16 weights current (te_policy_adam_step_bf16: no repack launches).  Refused
+    # when torch.distributed has more than one rank: the all-reduce sits between the gradient and the step, and the Python loop stays the
+    # path for that case.  The same kernels on the same inputs in the same order: the weights, the optimiser state and update()'s dict
+    # are bitwise what the Python loop gives.
+    # Measured on the MI355X (profiles/ppo_epoch.json), 8 minibatches per update(), ms per minibatch with the switch off
+    # against on: 0.247 against 0.261 (default), 0.419 against 0.420 ((128, 256, 512)) and 0.420 against 0.432 ((512, 128, 256)) at 8 192 rows,
+    # 1.260 / 2.762 / 3.122 against 1.266 / 2.762 / 3.135 at 65 536: no gain beyond the repeats' spread at any size, 3-5 % slower at some.
+    # The Python loop already enqueues ahead of the device; what the switch buys is an update with no Python between its kernels, not time.
+    # Off by default
+    fused_epoch: bool = False
 
     def __post_init__(self):
         for switch in SWITCH_NEEDS:
             refusal = missing_switch(self, switch)
             if refusal:
                 raise ValueError(refusal)
+        refusal = fused_epoch_needs(self)
+        if refusal:
+            raise ValueError(refusal)
 
 
 # switch: (the switch it needs, what it is to it), in the order PPOConfig checks them.  PPO checks them again, in its own order
@@ -603,6 +678,20 @@ def missing_switch(cfg: PPOConfig, switch: str) -> Optional[str]:
     """The refusal of `switch` when it is set without the switch it needs; None otherwise."""
     needs, what = SWITCH_NEEDS[switch]
     return f"PPOConfig.{switch} {what}: it needs {needs}" if getattr(cfg, switch) and not getattr(cfg, needs) else None
+
+
+FUSED_EPOCH_NEEDS = ("fused_update", "fused_optimizer", "fused_advantages")    # the calls te_policy_ppo_epoch chains
+
+
+def fused_epoch_needs(cfg: PPOConfig) -> Optional[str]:
+    """The refusal of fused_epoch when one of the three switches it needs is off (the first one, by name); None otherwise."""
+    if not cfg.fused_epoch:
+        return None
+    for needs in FUSED_EPOCH_NEEDS:
+        if not getattr(cfg, needs):
+            return (f"PPOConfig.fused_epoch enqueues te_adv_stats, the gradient call and te_policy_adam_step per minibatch from one "
+                    f"te_policy_ppo_epoch call: it needs {needs}")
+    return None
 
 
 class RolloutBuffer:
@@ -723,6 +812,8 @@ class PPO:
             self.fused_grad.bind_parameters()
             self.opt = PackedAdam(self.fused_grad, lr=self.cfg.learning_rate, eps=1e-5)
         self._grad_stats = torch.zeros(4, device=self.device)
+        if self.cfg.fused_epoch:        # te_policy_ppo_epoch's running sums: LOSS_KEYS and grad_norm, zeroed by every update()
+            self._epoch_sums = torch.zeros(5, device=self.device)
         if self.cfg.fused_advantages:   # allocated once, for the whole rollout: nothing grows under graph capture
             self._adv_stats = torch.zeros(2, device=self.device)         # the minibatch's (mean, std): te_policy_ppo_grad's adv_mean_std
             self._ev_stats = torch.zeros(4, device=self.device)          # (mean, std) of adv and of ret over the rollout
@@ -770,6 +861,14 @@ class PPO:
                 check_policy_shape(*policy_shape(self.policy))      # an unserved shape: the text that lists the served ones
             except ValueError as e:
                 return str(e)
+        if c.fused_epoch:               # its own rules, in front of the rules of the switches it needs
+            if fused_epoch_needs(c):
+                return fused_epoch_needs(c)
+            if not on_gpu:
+                return "PPOConfig.fused_epoch runs the HIP kernels of te_policy_ppo_epoch: it needs a GPU device"
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                return ("PPOConfig.fused_epoch chains the gradient and the optimiser step in one call, and with more than one "
+                        "torch.distributed rank the all-reduce sits between them: leave it off, update() then runs its Python loop")
         for switch, runs in (("fused_forward", "the HIP kernel te_policy_act"), ("fused_optimizer", "the HIP kernels of te_policy_adam_step"),
                              ("fused_update", "the HIP kernels of te_policy_ppo_grad"),
                              ("fused_advantages", "the HIP kernels of te_rollout_gae and te_adv_stats")):
@@ -942,8 +1041,16 @@ class PPO:
             adv_stats(adv, None, self._ev_stats[0:2], self._adv_ws)
             adv_stats(ret, None, self._ev_stats[2:4], self._adv_ws)
         amp = bool(c.fast_learner) and self.device.type == "cuda" and not c.fused_update
+        if c.fused_epoch:               # the weights Adam reads are the buffer; the bf16 copies are rounded once, then kept by the step
+            self.fused_grad.refresh()
+            acc = self._epoch_sums.zero_()
         for _ in range(c.n_epochs):
             perm = torch.randperm(T * N, device=self.device)
+            if c.fused_epoch:           # every minibatch of the epoch: one call, no return to Python in between
+                self.fused_grad.ppo_epoch(obs, perm, c.batch_size, actions, old_logp, adv, ret, c.clip_range, c.vf_coef, c.ent_coef,
+                                          self._flat_grad, self.opt, c.max_grad_norm, self._adv_ws, self._adv_stats, self._grad_stats, acc)
+                n_batches += -(-(T * N) // c.batch_size)
+                continue
             for s in range(0, T * N, c.batch_size):
                 idx = perm[s:s + c.batch_size]
                 if self.fused_grad is not None:

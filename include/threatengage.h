@@ -32,7 +32,7 @@ extern "C" {
 #endif
 
 #define TE_ABI_VERSION 5   /* layout of te_config / the state blob.  Added since without a layout change: the task presets 10-12, TE_REWARD_L5_C1,
-                              bit 1 of te_config.evaluation (TE_EVAL_ORIGIN_RULE), te_drive_wingman_bf16 */
+                              bit 1 of te_config.evaluation (TE_EVAL_ORIGIN_RULE), te_drive_wingman_bf16, te_policy_adam_step_bf16, te_policy_ppo_epoch */
 
 /* ---- tasks (reference env class each one mirrors) ----------------------- */
 enum {
@@ -661,6 +661,71 @@ int te_rollout_gae(int32_t n_steps, int32_t n_envs, const float* rewards, const 
 int te_adv_stats_workspace_bytes(int64_t n, size_t* out_bytes);
 int te_adv_stats(const float* x, const int64_t* index, int64_t n, float* out_mean_std, void* workspace, size_t workspace_bytes,
                  void* stream);
+
+/* The optimiser step that leaves the bf16 copies of the weights current: the step above on the packed buffer of a served
+ * te_policy_shape (words is that shape's parameter count), where the thread that has just computed a word of a weight layer also stores
+ * its bf16 rounding (nearest-even, the conversion of the pack calls) at its place in weights_bf16 ([n][Kp], the layout of the bf16 pack
+ * call) and, when weights_bf16_t is not NULL and the layer has a block there, in weights_bf16_t ([k][Np], the layout of the transposed
+ * pack call).  Biases, mu, value and log_std have no bf16 copy.  The arithmetic of the step is the same code: params and state end up
+ * bitwise as the plain step leaves them, and afterwards both bf16 buffers are bitwise what the two pack calls give on the stepped
+ * params, so no repack launch follows a step.
+ * REQUIREMENT: the pad columns of the bf16 buffers are never written here.  Both buffers must have been packed once by their pack call
+ * (any params of this shape) before the first step; the pad columns keep the zeros of that pack.
+ * Still two launches on `stream`, no atomics, no allocation, no host synchronisation; a HIP graph can capture the call; bitwise
+ * repeatable.  Checks: the plain step's, plus: the shape is served (as in the shape check), weights_bf16 is not NULL and 16-byte
+ * aligned, weights_bf16_t is 16-byte aligned when given.  Every refusal returns before anything is launched. */
+int te_policy_adam_step_bf16(float* params, const float* grad, void* state, size_t state_bytes, const te_policy_shape* shape,
+                             uint16_t* weights_bf16, uint16_t* weights_bf16_t, double lr, double beta1, double beta2, double eps,
+                             float max_grad_norm, float grad_scale, void* stream);
+
+/* One epoch of the PPO update enqueued by one call: the four calls of a minibatch (advantage statistics, gradient, optimiser step, the
+ * log's running sums), for every minibatch of a permutation, without a return to the caller in between.
+ * For k = 0, 1, ... with s = k * batch < n_perm and b = min(batch, n_perm - s), in this order on `stream`:
+ *   1. the statistics call on (adv, perm + s, b) into adv_mean_std (adv_workspace: at least the statistics workspace of
+ *      min(batch, n_perm) elements);
+ *   2. the gradient call over the rows index = perm + s, b of them, with adv_mean_std, into grad and stats (workspace: at least the
+ *      gradient workspace of min(batch, n_perm) rows, of the precision chosen below);
+ *   3. the optimiser step on params with grad;
+ *   4. one single-thread launch: sums[0..3] += stats[0..3] (pg, vl, ent, clip_frac), sums[4] += the state's norm word (the gradient's
+ *      norm before clipping), in fp32.  sums is added to, never cleared: the caller zeroes it when its log starts.
+ * weights_bf16 and weights_bf16_t both NULL: the fp32 shaped gradient call and the plain step.  Both given: the bf16 gradient call and
+ * the step that keeps them current (above; its requirement holds here: both packed once, and current with params when the call
+ * starts).  Exactly one given is refused.
+ * Everything the calls would write is bitwise what the same calls give when made one by one.  perm is int64 on the device, not
+ * range-checked, and required.  The call allocates nothing and never synchronises with the host.  EVERY check is made before the
+ * first launch: struct_size == sizeof(te_ppo_epoch_args), a served shape, batch >= 1, 1 <= n_perm <= 2^40, and every check of the four inner
+ * calls for the first and for the last (shortest) minibatch; a refusal leaves every buffer as it was, with te_last_error set. */
+typedef struct te_ppo_epoch_args {
+  size_t struct_size;                       /* sizeof(te_ppo_epoch_args), set by the caller */
+  te_policy_shape shape;
+  float* params;                            /* the packed fp32 buffer, stepped in place */
+  uint16_t* weights_bf16;                   /* both NULL: fp32; both given: bf16, kept current by the step */
+  uint16_t* weights_bf16_t;
+  const float* lidar;                       /* the rollout's row arrays, as the gradient call reads them */
+  const float* inertial;
+  const float* last_action;
+  const float* action;
+  const float* old_logp;
+  const float* adv;
+  const float* ret;
+  const int64_t* perm;                      /* device, n_perm row numbers */
+  int64_t n_perm;
+  int32_t batch;                            /* rows per minibatch; the last one may be shorter */
+  float clip_range, vf_coef, ent_coef;
+  float* grad;                              /* the packed gradient: the last minibatch's when the call ends */
+  void* state;                              /* the optimiser's state buffer */
+  size_t state_bytes;
+  double lr, beta1, beta2, eps;
+  float max_grad_norm, grad_scale;
+  void* workspace;                          /* the gradient workspace, 256-byte aligned */
+  size_t workspace_bytes;
+  void* adv_workspace;                      /* the statistics workspace */
+  size_t adv_workspace_bytes;
+  float* adv_mean_std;                      /* device scratch [2] */
+  float* stats;                             /* device scratch [4] */
+  float* sums;                              /* device [5]: pg, vl, ent, clip_frac, grad_norm; added to */
+} te_ppo_epoch_args;
+int te_policy_ppo_epoch(const te_ppo_epoch_args* args, void* stream);
 
 /* Episode monitor: the bookkeeping of SB3's VecMonitor.step_wait (episode return and length per env, `infos[i]["episode"]`), of
  * its logger's ep_rew_mean / ep_len_mean window, and of evaluate_policy's per-env episode quotas (what the reference's
