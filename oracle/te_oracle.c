@@ -82,6 +82,8 @@ typedef struct ote_env {
   float* out_stacked; uint8_t* out_mask; float* out_t_stacked; uint8_t* out_t_mask;
   /* ote_step_students: [N,P,...] outputs of the step in flight */
   float* st_stacked; uint8_t* st_mask; float* st_inertial; float* st_last_action; uint8_t* st_active;
+  /* flight census of the last step, [N*D] each (ote_set_flight_census; NULL = off, the default) */
+  uint32_t* census; double* census_margin;
 } ote_env;
 
 /* ------------------------------------------------------------------------- */
@@ -244,7 +246,8 @@ static void observe(ote_drone* d) {
 /* QuadX.update_control, flight mode 6 (vx, vy, vr, vz; quadcopter.py:152,408-413) or mode 7
  * (x, y, r, z; level2/components/quadcopter_manager.py:68).  Runs on EVERY physics sub-step
  * with the PID period still control_dt (level4_simulation.py:92-94). */
-static void control(const te_config* c, ote_drone* d, int mode, real pwm[4]) {
+/* the cascade up to the motor mix: pwm[] before the saturation handling */
+static void control_mix(const te_config* c, ote_drone* d, int mode, real pwm[4]) {
   const te_quad_params* q = &c->quad;
   const real T = (real)c->control_dt;
   real a0 = d->setpoint[0], a1 = d->setpoint[1], a2 = d->setpoint[2], z = d->setpoint[3];
@@ -282,12 +285,19 @@ static void control(const te_config* c, ote_drone* d, int mode, real pwm[4]) {
   pwm[1] = +tq[0] + tq[1] + tq[2] + th;
   pwm[2] = -tq[0] + tq[1] - tq[2] + th;
   pwm[3] = +tq[0] - tq[1] - tq[2] + th;
-  /* saturation handling */
+}
+/* saturation handling */
+static void pwm_limits(const te_config* c, real pwm[4]) {
+  const te_quad_params* q = &c->quad;
   real hi = fmax(fmax(pwm[0], pwm[1]), fmax(pwm[2], pwm[3]));
   if (hi > (real)1) for (int i = 0; i < 4; ++i) pwm[i] /= hi;
   real lo = fmin(fmin(pwm[0], pwm[1]), fmin(pwm[2], pwm[3]));
   real fl = (real)q->pwm_floor;
   if (lo < fl) for (int i = 0; i < 4; ++i) pwm[i] += ((real)1 - pwm[i]) / ((real)1 - lo) * (fl - lo);
+}
+static void control(const te_config* c, ote_drone* d, int mode, real pwm[4]) {
+  control_mix(c, d, mode, pwm);
+  pwm_limits(c, pwm);
 }
 
 /* Motors.physics_update + BoringBodies.physics_update + rotational drag: body-frame force and
@@ -399,11 +409,67 @@ static void motor_noise(const ote_env* E, int e, int slot, uint32_t step_index, 
   out[0] = r0 * cos(a0); out[1] = r0 * sin(a0); out[2] = r1 * cos(a1); out[3] = r1 * sin(a1);
 }
 
+/* Flight census (ote_set_flight_census; test instrumentation, off by default): which paths of the sub-step a drone took during the
+ * last step, one bit each, and how close any of its IMU reads came to the gimbal guard's threshold.  Every bit is decided here from
+ * the oracle's own values in its own precision; the tests use them to know that a crafted state flies the path it was crafted for
+ * and to leave out drones whose guard decision float32 rounding may flip. */
+enum { OTE_CENSUS_GENERAL = 1,    /* outside the central branch of both inverse functions: not (R22 > 0, |R21| <= tan(pi/8) R22, |sarg| <= 0.5) */
+       OTE_CENSUS_GUARD = 2,      /* getEulerFromQuaternion's |sarg| >= 0.99999 */
+       OTE_CENSUS_SATURATED = 4,  /* the motor mix's largest pwm > 1 */
+       OTE_CENSUS_FLOORED = 8,    /* its smallest pwm < pwm_floor (after the saturation handling) */
+       OTE_CENSUS_FAST = 16,      /* (dt |w| / 2)^2 >= 0.25 on the rate the attitude update uses */
+       OTE_CENSUS_GROUND = 32 };  /* the ground contact taken */
+#define OTE_GUARD_SARG ((real)0.99999)
+static real census_sarg(const ote_drone* d) { return (real)-2 * (d->quat[0] * d->quat[2] - d->quat[3] * d->quat[1]); }
+/* one IMU read (a sub-step's, or the epilogue's when cfg.observe_lag == 0): distance of |sarg| to the guard's threshold */
+static void census_read(const ote_env* E, int e, int slot, const ote_drone* d) {
+  const double mg = fabs((double)fabs(census_sarg(d)) - (double)OTE_GUARD_SARG);
+  double* at = &E->census_margin[(size_t)e * E->D + slot];
+  if (mg < *at) *at = mg;
+}
+/* one sub-step, flown on a COPY of the drone (with the ground plane taken away, so that the copy's height says whether the contact
+ * would be taken): the drone itself is untouched and substep() then flies it as if the census did not exist */
+static void census_substep(const ote_env* E, int e, int slot, const ote_drone* d, int mode, uint32_t step_index, int sub) {
+  te_config c = E->cfg;
+  c.ground_contact = 0;
+  ote_drone t = *d;
+  uint32_t bits = 0;
+  real nz[4], Fb[3], Tb[3], Fw[3], Tw[3], m[9];
+  observe(&t);
+  census_read(E, e, slot, &t);
+  quat_to_mat(t.quat, m);
+  const real sarg = census_sarg(&t);
+  if (!(m[8] > 0 && fabs(m[7]) <= (real)0.4142135623730950488 * m[8] && fabs(sarg) <= (real)0.5)) bits |= OTE_CENSUS_GENERAL;
+  if (fabs(sarg) >= OTE_GUARD_SARG) bits |= OTE_CENSUS_GUARD;
+  int ratio = (int)((real)c.control_dt / (real)c.physics_dt + (real)0.5);
+  if (ratio < 1) ratio = 1;
+  if (c.control_every_substep || sub % ratio == 0) {
+    control_mix(&c, &t, mode, t.pwm);
+    const real hi = fmax(fmax(t.pwm[0], t.pwm[1]), fmax(t.pwm[2], t.pwm[3]));
+    if (hi > (real)1) bits |= OTE_CENSUS_SATURATED;
+    const real s = hi > (real)1 ? hi : (real)1;
+    const real lo = fmin(fmin(t.pwm[0] / s, t.pwm[1] / s), fmin(t.pwm[2] / s, t.pwm[3] / s));
+    if (lo < (real)c.quad.pwm_floor) bits |= OTE_CENSUS_FLOORED;
+    pwm_limits(&c, t.pwm);
+  }
+  motor_noise(E, e, slot, step_index, sub, nz);
+  actuate(&c, &t, t.pwm, nz, Fb, Tb);
+  mat_vec(m, Fb, Fw);
+  mat_vec(m, Tb, Tw);
+  for (int i = 0; i < 3; ++i) { Fw[i] += t.pending[i]; Tw[i] += t.pending[3 + i]; }
+  integrate(&c, &t, Fw, Tw);
+  const real half = (real)0.5 * (real)c.physics_dt * norm3(t.omega);
+  if (half * half >= (real)0.25) bits |= OTE_CENSUS_FAST;
+  if (E->cfg.ground_contact && t.pos[2] < (real)c.ground_z + (real)c.hull_half_height) bits |= OTE_CENSUS_GROUND;
+  E->census[(size_t)e * E->D + slot] |= bits;
+}
+
 /* One physics sub-step of one armed drone: L{2,4}AviarySimulation.step inner body
  * (level4_simulation.py:87-98): update_imu -> update_control -> update_physics -> stepSimulation */
 static void substep(const ote_env* E, int e, int slot, ote_drone* d, int mode, uint32_t step_index, int sub) {
   const te_config* c = &E->cfg;
   real nz[4], Fb[3], Tb[3], Fw[3], Tw[3], m[9];
+  if (E->census) census_substep(E, e, slot, d, mode, step_index, sub);
   observe(d);
   /* the reference's loop calls update_control on every physics sub-step (level4_simulation.py:92-94); PyFlyt's own Aviary
    * calls it on every (physics_hz / ctrl_hz)-th one (cfg.control_every_substep == 0) and the motors keep the last pwm */
@@ -1179,7 +1245,7 @@ static void level4_step_env(ote_env* E, int e, const float* action, float* lidar
     for (int i = 0; i < D; ++i)
       if (dr[i].armed) substep(E, e, i, &dr[i], 6, step_index, s);
   if (!c->observe_lag)
-    for (int i = 0; i < D; ++i) if (dr[i].armed) observe(&dr[i]);
+    for (int i = 0; i < D; ++i) if (dr[i].armed) { observe(&dr[i]); if (E->census) census_read(E, e, i, &dr[i]); }
   er->step += 1; /* AGENT_STEP_BROADCAST: guns, task and LIDAR buffers see the new step */
   const int step = er->step;
 
@@ -1483,7 +1549,7 @@ static void stage02_step_env(ote_env* E, int e, const float* action, float* lida
     for (int i = 0; i < D; ++i)
       if (dr[i].armed) substep(E, e, i, &dr[i], 6, step_index, s);
   if (!c->observe_lag)
-    for (int i = 0; i < D; ++i) if (dr[i].armed) observe(&dr[i]);
+    for (int i = 0; i < D; ++i) if (dr[i].armed) { observe(&dr[i]); if (E->census) census_read(E, e, i, &dr[i]); }
   er->step += 1;
   const int step = er->step;
   /* on_step_middle (stages.py:144-179) */
@@ -1638,7 +1704,7 @@ static void stage01_step_env(ote_env* E, int e, const float* action, float* lida
   /* simulation.drones order: invader, pursuer0, pursuer1 (independent bodies: order immaterial) */
   for (int s = 0; s < c->substeps; ++s)
     for (int i = 0; i < D; ++i) substep(E, e, i, &dr[i], i == 2 ? 7 : 6, step_index, s);
-  if (!c->observe_lag) for (int i = 0; i < D; ++i) observe(&dr[i]);
+  if (!c->observe_lag) for (int i = 0; i < D; ++i) { observe(&dr[i]); if (E->census) census_read(E, e, i, &dr[i]); }
   /* observation first (:137), then reward / termination */
   float* L; float* In; float* La;
   real d = dist3(dr[2].obs_pos, dr[0].obs_pos);
@@ -1712,7 +1778,29 @@ OTE_API ote_env* ote_create(const te_config* cfg) {
 }
 OTE_API void ote_destroy(ote_env* E) {
   if (!E) return;
-  free(E->drones); free(E->envs); free(E->margin); free(E->margin_state); free(E->margin_stack); free(E->ring); free(E);
+  free(E->drones); free(E->envs); free(E->margin); free(E->margin_state); free(E->margin_stack); free(E->ring);
+  free(E->census); free(E->census_margin); free(E);
+}
+/* Flight census (see census_substep): on = 1 makes every later step record, per drone, the sub-step paths it took and its closest IMU
+ * read to the gimbal guard; on = 0 (the default) drops the records and leaves the step with one untaken branch per sub-step. */
+OTE_API int ote_set_flight_census(ote_env* E, int on) {
+  const size_t n = (size_t)E->cfg.n_envs * E->D;
+  free(E->census); free(E->census_margin);
+  E->census = NULL; E->census_margin = NULL;
+  if (!on) return 0;
+  E->census = (uint32_t*)calloc(n, sizeof(uint32_t));
+  E->census_margin = (double*)calloc(n, sizeof(double));
+  if (!E->census || !E->census_margin) { free(E->census); free(E->census_margin); E->census = NULL; E->census_margin = NULL; return 1; }
+  for (size_t i = 0; i < n; ++i) E->census_margin[i] = 1e30;
+  return 0;
+}
+/* branches [N*D] u32 (OTE_CENSUS_* bits ORed over the last step's sub-steps), guard_margin [N*D] f64 (1e30: the drone did not fly) */
+OTE_API int ote_flight_census(const ote_env* E, uint32_t* branches, double* guard_margin) {
+  if (!E->census) return 1;
+  const size_t n = (size_t)E->cfg.n_envs * E->D;
+  memcpy(branches, E->census, n * sizeof(uint32_t));
+  memcpy(guard_margin, E->census_margin, n * sizeof(double));
+  return 0;
 }
 OTE_API int ote_real_bytes(void) { return (int)sizeof(real); }
 OTE_API int ote_reset(ote_env* E, const uint8_t* mask) {
@@ -1792,6 +1880,8 @@ OTE_API int ote_step(ote_env* E, const float* actions, float* lidar, float* iner
                      uint8_t* done, int32_t* info, float* t_lidar, float* t_inertial, float* t_last_action, int threads) {
   const int N = E->cfg.n_envs;
   (void)threads;
+  if (E->census)
+    for (size_t i = 0; i < (size_t)N * E->D; ++i) { E->census[i] = 0; E->census_margin[i] = 1e30; }
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
 #endif

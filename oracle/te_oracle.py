@@ -60,6 +60,8 @@ def lib(precision: str = "f64") -> C.CDLL:
         L.ote_stack_draws.argtypes = [C.POINTER(K.Config), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
         L.ote_state_margins.argtypes = [C.c_void_p, C.c_void_p]
         L.ote_random_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.ote_set_flight_census.argtypes = [C.c_void_p, C.c_int]
+        L.ote_flight_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.te_config_default.argtypes = [C.POINTER(K.Config), C.c_int32]
         L.te_quad_preset.argtypes = [C.POINTER(K.Config), C.c_int32]
         L.ote_degrees_between.restype = C.c_double
@@ -81,6 +83,10 @@ def default_config(task, **overrides) -> K.Config:
         if lib("f64").te_quad_preset(C.byref(cfg), int(overrides.pop("quad_preset"))):
             raise ValueError("unknown quad_preset")
     return K.apply_overrides(cfg, **overrides)
+
+
+# bits of OracleEnv.flight_census() (OTE_CENSUS_* in te_oracle.c)
+CENSUS_GENERAL, CENSUS_GUARD, CENSUS_SATURATED, CENSUS_FLOORED, CENSUS_FAST, CENSUS_GROUND = 1, 2, 4, 8, 16, 32
 
 
 def _p(a: Optional[np.ndarray]):
@@ -225,6 +231,18 @@ class OracleEnv:
         out = np.empty(self.N, np.float64)
         self.L.ote_state_margins(self.h, _p(out))
         return out
+
+    def set_flight_census(self, on: bool = True):
+        """Record, from the next step on, which sub-step paths every drone takes (CENSUS_* bits).  Off by default."""
+        assert self.L.ote_set_flight_census(self.h, int(bool(on))) == 0
+
+    def flight_census(self):
+        """(branches [N,D] uint32, guard_margin [N,D] float64) of the last step: the CENSUS_* bits ORed over its sub-steps, and the
+        smallest | |sarg| - 0.99999 | over every IMU read of the step (1e30 for a drone that did not fly)."""
+        branches = np.empty((self.N, self.D), np.uint32)
+        margin = np.empty((self.N, self.D), np.float64)
+        assert self.L.ote_flight_census(self.h, _p(branches), _p(margin)) == 0, "flight_census needs set_flight_census(True)"
+        return branches, margin
 
     def random_actions(self, seed: int, step_index: int) -> np.ndarray:
         a = np.empty((self.N, 4), np.float32)
