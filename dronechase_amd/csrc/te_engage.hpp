@@ -87,18 +87,26 @@ TE_DEV V3 x_mul(const M3& R, V3 v) {
   return V3{xfma(R.m02, v.z, xfma(R.m01, v.y, R.m00 * v.x)), xfma(R.m12, v.z, xfma(R.m11, v.y, R.m10 * v.x)), xfma(R.m22, v.z, xfma(R.m21, v.y, R.m20 * v.x))};
 }
 // lidar_cell (te_logic.hpp) on the native sqrt / rcp and the polynomial asin / atan2 of the sub-step loop (1e-7 abs): a tenth of
-// libm's acosf + atan2f instructions, which were a third of this kernel's straight-line path
-TE_DEV void lidar_cell_fast(const te_config& c, V3 local, int& cell, float& rhat) {
+// libm's acosf + atan2f instructions, which were a third of this kernel's straight-line path.
+// The RANGE is taken from the world-frame difference `d`, not from the rotated vector: R comes out of float32 Euler angles and is
+// orthonormal to a few 1e-7 only, so |R d| sat up to 9.4e-6 m from |d| at the rim R = 40 (tests/test_gpu_lidar_edges.py, rim), and a rotation
+// changes no length.  One Newton step each brings the square root and the quotient within half an ulp in nearly all cases (v_rsq_f32 and
+// v_rcp_f32 are 1 ulp apiece, 2.4e-6 m each at the rim): five instructions.  The angles take the rotated direction.
+TE_DEV void lidar_cell_fast(const te_config& c, const M3& R, V3 d, int& cell, float& rhat) {
   TE_EXACT
-  const float r2 = xfma(local.z, local.z, xfma(local.y, local.y, local.x * local.x));
+  const V3 local = x_mul(R, d);
+  const float r2 = xfma(d.z, d.z, xfma(d.y, d.y, d.x * d.x));
   float theta = 0.0f, phi = 0.0f, r = 0.0f;
   if (r2 != 0.0f) {
     const float inv = rsq(r2);
     r = r2 * inv;
+    r = xfma(xfma(-r, r, r2), 0.5f * inv, r);
     theta = 0.5f * kPi - x_asin(clampf(local.z * inv, -1.0f, 1.0f));
     phi = x_atan2(local.y, local.x);
   }
-  rhat = clampf(r * rcp(c.lidar_radius), 0.0f, 1.0f);
+  const float inv_radius = rcp(c.lidar_radius);
+  const float q = r * inv_radius;
+  rhat = clampf(xfma(xfma(-q, c.lidar_radius, r), inv_radius, q), 0.0f, 1.0f);
   const int ti = min(max((int)(theta * (1.0f / kPi) * (float)TE_LIDAR_NTHETA), 0), TE_LIDAR_NTHETA - 1);
   const int pi = min(max((int)((phi + kPi) * (0.5f / kPi) * (float)TE_LIDAR_NPHI), 0), TE_LIDAR_NPHI - 1);
   cell = ti * TE_LIDAR_NPHI + pi;
@@ -446,7 +454,7 @@ __global__ __launch_bounds__(64) void engage_kernel(Params p, const float* __res
 #pragma unroll
     for (int j = 1; j < DM; ++j) {   // a slot somebody of the chunk has armed is binned in every lane (branch-free, as above); only armed ones may own a cell
       if (!(j < D && ((live >> j) & 1u))) continue;   // wave-uniform: nobody has it armed, nobody looks at its cell (owners stays clear)
-      int cj; lidar_cell_fast(c, x_mul(R, sub(V3{px[j], py[j], pz[j]}, apos)), cj, rhat[j]);
+      int cj; lidar_cell_fast(c, R, sub(V3{px[j], py[j], pz[j]}, apos), cj, rhat[j]);
       cell[j] = (uint32_t)cj;
       const bool in = ((A >> j) & one) != 0;
       M same = 0;           // the current owner of the same cell, if any (at most one)
@@ -758,7 +766,7 @@ TE_DEV uint32_t own_sphere_regs(const te_config& c, int D, const float (&px)[DM]
   cell[0] = 0u; rhat[0] = 1.0f;
 #pragma unroll
   for (int j = 1; j < DM; ++j) {
-    int cj; lidar_cell_fast(c, x_mul(R, sub(V3{px[j], py[j], pz[j]}, apos)), cj, rhat[j]);
+    int cj; lidar_cell_fast(c, R, sub(V3{px[j], py[j], pz[j]}, apos), cj, rhat[j]);
     cell[j] = (uint32_t)cj;
     const bool in = j < D && ((A >> j) & 1u) != 0u;
     uint32_t same = 0u; float r_owner = 2.0f;

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(DM * 64) __attribute__((amdgpu_waves_per_eu(6, 10))
   int cj = 0; float rh = 1.0f;
   if (s >= 1) {
     const M3 Rm = x_inverse_attitude(ag[0], ag[1], ag[2]);
-    lidar_cell_fast(c, x_mul(Rm, sub(V3{mx, my, mz}, apos)), cj, rh);
+    lidar_cell_fast(c, Rm, sub(V3{mx, my, mz}, apos), cj, rh);
     *reinterpret_cast<uint2*>(&sm[R.cellr(s) * 64 + 2 * lane]) = make_uint2((uint32_t)cj, __float_as_uint(rh));
   }
   TE_WSTAMP(2, 0);
@@ -555,7 +555,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(SPW == 1 ?
 #pragma unroll
     for (int u = 0; u < SPW; ++u) {
       if (has[u] && sl[u] >= 1) {
-        lidar_cell_fast(c, x_mul(Rm, sub(V3{mx[u], my[u], mz[u]}, apos0)), cj[u], rh[u]);
+        lidar_cell_fast(c, Rm, sub(V3{mx[u], my[u], mz[u]}, apos0), cj[u], rh[u]);
         *reinterpret_cast<uint2*>(&sm[R.cellr(sl[u]) * 64 + 2 * lane]) = make_uint2((uint32_t)cj[u], __float_as_uint(rh[u]));
       }
     }
@@ -983,7 +983,7 @@ __global__ __launch_bounds__(DM * 64) void engage_slots_stage02_kernel(Params p,
   int cj = 0; float rh = 1.0f;
   if (s >= 1) {
     const M3 Rm = x_inverse_attitude(ag[0], ag[1], ag[2]);
-    lidar_cell_fast(c, x_mul(Rm, sub(V3{mx, my, mz}, apos)), cj, rh);
+    lidar_cell_fast(c, Rm, sub(V3{mx, my, mz}, apos), cj, rh);
     *reinterpret_cast<uint2*>(&sm[R.cellr(s) * 64 + 2 * lane]) = make_uint2((uint32_t)cj, __float_as_uint(rh));
   }
   if (is_p) {   // closest invader, shoot_by_ids with the suicide rule (level3/components/quadcopter_manager.py:155-171), explosion

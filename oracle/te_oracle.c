@@ -84,6 +84,9 @@ typedef struct ote_env {
   float* st_stacked; uint8_t* st_mask; float* st_inertial; float* st_last_action; uint8_t* st_active;
   /* flight census of the last step, [N*D] each (ote_set_flight_census; NULL = off, the default) */
   uint32_t* census; double* census_margin;
+  /* [N] sphere_margins of the agent's tile built by the last step / observe, the terminal tile when that is the one built
+   * (ote_set_lidar_margins; NULL = off, the default) */
+  double* margin_lidar;
 } ote_env;
 
 /* ------------------------------------------------------------------------- */
@@ -831,6 +834,14 @@ static void own_sphere(const te_config* c, const ote_drone* dr, int D, int own, 
 }
 static void own_sphere3(const te_config* c, const ote_drone* dr, int D, int own, float* sphere) {
   for (int i = 0; i < TE_OBS_LIDAR_WORDS; ++i) sphere[i] = 1.0f;
+  /* the closest range of every cell so far, in the build's precision.  A DEPARTURE from the reference, on purpose: its sphere is float32 and
+   * add_features compares the new range with the stored, rounded cell (lidar_math.py:298-301), which ote_add_features above still mirrors.
+   * With float64 ranges that lets the rounding's direction decide between two drones less than a float32 ulp apart, and hands a cell to the
+   * LATER of two drones at one position whenever the first one's range rounded up.  The reference's own ranges are float32 (rounding is then
+   * the identity, the lower slot wins, as in the float32 build and the kernels); the high-precision build keeps the unrounded best so that it
+   * states the same rule (tests/_lidar_states.py: ties). */
+  real best[TE_LIDAR_CELLS];
+  for (int i = 0; i < TE_LIDAR_CELLS; ++i) best[i] = (real)1;
   real q[4];
   quat_from_euler(dr[own].obs_euler, q);
   for (int k = 0; k < 4; ++k) q[k] = (real)(float)q[k];
@@ -841,13 +852,92 @@ static void own_sphere3(const te_config* c, const ote_drone* dr, int D, int own,
     cartesian_to_spherical(local, sph);
     real rhat = clampr(sph[0] / (real)c->lidar_radius, (real)0, (real)1);
     int cell = theta_index(sph[1]) * TE_LIDAR_NPHI + phi_index(sph[2]);
-    if (rhat < (real)sphere[cell]) {
+    if (rhat < best[cell]) {
       int type = j < c->n_pursuers ? TE_TYPE_LOYALWINGMAN : TE_TYPE_LOITERINGMUNITION;
+      best[cell] = rhat;
       sphere[cell] = (float)rhat;
       sphere[TE_LIDAR_CELLS + cell] = (float)((real)type / (real)5);
       sphere[2 * TE_LIDAR_CELLS + cell] = (float)((real)1 / (real)10);
     }
   }
+}
+
+/* How decidable the own sphere of `own` is (test instrumentation; tests/_lidar_states.py).  For every OTHER armed drone j: its cell, its
+ * r_hat, and a decision margin in METRES, i.e. how far j would have to move for the tile to change.  A target at or beyond the rim
+ * (r_hat == 1: invisible) changes the tile only by coming inside: |r - R|.  A visible one has the smallest of
+ *   theta edge  r |theta - nearest INTERIOR edge k pi / 13, k = 1..12|   (the index is clipped at 0 and pi: no edge there)
+ *   phi edge    r sin(theta) |phi - nearest edge -pi + k 2 pi / 26, k = 0..26|   (k = 0 and 26: the seam between columns 0 and 25)
+ *   rim         |r - R|
+ *   tie         |r_j - r_k| for every other armed k of the same cell, unless both are beyond the rim or the float32 positions of j and k
+ *               are bitwise identical (then closer-wins is decided by the slot order, not by a range).
+ * A drone at the observer's exact position (r == 0: cell (0, 13) by definition) has no direction and therefore no angular term.
+ * cell = -1, margin = 1e30 for own, for a disarmed slot.  Returns the smallest margin (1e30 if nothing is armed). */
+static real sphere_margins(const te_config* c, const ote_drone* dr, int D, int own, int32_t* cell, double* rhat, double* margin) {
+  real r_of[OTE_MAX_DRONES], m_of[OTE_MAX_DRONES];
+  int cell_of[OTE_MAX_DRONES];
+  const real R = (real)c->lidar_radius, BIG = (real)1e30;
+  real q[4];
+  quat_from_euler(dr[own].obs_euler, q);
+  for (int k = 0; k < 4; ++k) q[k] = (real)(float)q[k];
+  for (int j = 0; j < D; ++j) {
+    cell_of[j] = -1; r_of[j] = 0; m_of[j] = BIG;
+    if (j == own || !dr[j].armed) continue;
+    real local[3], sph[3];
+    reframe_origin(dr[j].obs_pos, dr[own].obs_pos, q, local);
+    cartesian_to_spherical(local, sph);
+    const real r = sph[0];
+    cell_of[j] = theta_index(sph[1]) * TE_LIDAR_NPHI + phi_index(sph[2]);
+    r_of[j] = r;
+    real m = fabs(r - R);
+    if (r < R && r != 0) {
+      const real dth = OTE_PI / (real)TE_LIDAR_NTHETA, dph = (real)2 * OTE_PI / (real)TE_LIDAR_NPHI;
+      real k = floor(sph[1] / dth + (real)0.5);
+      k = k < 1 ? 1 : (k > TE_LIDAR_NTHETA - 1 ? TE_LIDAR_NTHETA - 1 : k);
+      const real mt = r * fabs(sph[1] - k * dth);
+      const real kp = floor((sph[2] + OTE_PI) / dph + (real)0.5);
+      const real mp = r * sin(sph[1]) * fabs(sph[2] - (kp * dph - OTE_PI));
+      if (mt < m) m = mt;
+      if (mp < m) m = mp;
+    }
+    m_of[j] = m;
+  }
+  real least = BIG;
+  for (int j = 0; j < D; ++j) {
+    if (cell_of[j] < 0) continue;
+    for (int k = 0; k < D; ++k) {
+      if (k == j || cell_of[k] != cell_of[j] || (r_of[j] >= R && r_of[k] >= R)) continue;
+      if ((float)dr[j].obs_pos[0] == (float)dr[k].obs_pos[0] && (float)dr[j].obs_pos[1] == (float)dr[k].obs_pos[1] &&
+          (float)dr[j].obs_pos[2] == (float)dr[k].obs_pos[2]) continue;
+      const real t = fabs(r_of[j] - r_of[k]);
+      if (t < m_of[j]) m_of[j] = t;
+    }
+    if (m_of[j] < least) least = m_of[j];
+  }
+  for (int j = 0; j < D; ++j) {
+    if (cell) cell[j] = cell_of[j];
+    if (rhat) rhat[j] = cell_of[j] < 0 ? 1.0 : (double)clampr(r_of[j] / R, (real)0, (real)1);
+    if (margin) margin[j] = (double)m_of[j];
+  }
+  return least;
+}
+
+static void poses_to_drones(te_config* c, ote_drone* dr, int D, int P, const double* pos, const double* euler_own, int own,
+                            const uint8_t* armed, double lidar_radius) {
+  memset(c, 0, sizeof *c);
+  c->n_pursuers = P; c->n_invaders = D - P; c->lidar_radius = (float)lidar_radius;
+  memset(dr, 0, sizeof(ote_drone) * OTE_MAX_DRONES);
+  for (int i = 0; i < D; ++i) {
+    for (int k = 0; k < 3; ++k) dr[i].obs_pos[k] = (real)pos[3 * i + k];
+    dr[i].armed = armed[i];
+  }
+  for (int k = 0; k < 3; ++k) dr[own].obs_euler[k] = (real)euler_own[k];
+}
+/* sphere_margins from raw poses, the arguments of ote_own_sphere_from_poses: cell [D] (-1: not a target), rhat [D], margin [D] (metres) */
+OTE_API void ote_own_sphere_margins(int D, int P, const double* pos, const double* euler_own, int own, const uint8_t* armed,
+                                    double lidar_radius, int32_t* cell, double* rhat, double* margin) {
+  te_config c; ote_drone dr[OTE_MAX_DRONES];
+  poses_to_drones(&c, dr, D, P, pos, euler_own, own, armed, lidar_radius);
+  sphere_margins(&c, dr, D, own, cell, rhat, margin);
 }
 
 /* own sphere from raw poses (golden fixture io_data0.h5 cross-check) */
@@ -1418,7 +1508,7 @@ static void level4_step_env(ote_env* E, int e, const float* action, float* lidar
   float* L = to_terminal && t_lidar ? t_lidar : lidar;
   float* In = to_terminal && t_inertial ? t_inertial : inertial;
   float* La = to_terminal && t_last_action ? t_last_action : last_action;
-  if (L) own_sphere(c, dr, D, 0, L);
+  if (L) { own_sphere(c, dr, D, 0, L); if (E->margin_lidar) E->margin_lidar[e] = (double)sphere_margins(c, dr, D, 0, NULL, NULL, NULL); }
   if (In) inertial_obs(c, &dr[0], step, max_munition_of(c, 0), In);
   if (La) for (int k = 0; k < 4; ++k) La[k] = (float)er->last_action[k];
   if (c->stacked_obs) { /* level5_envrionment.py:312-351: every wingman's update_lidar, then the agent's stack */
@@ -1620,7 +1710,7 @@ static void stage02_step_env(ote_env* E, int e, const float* action, float* lida
   float* L = to_terminal && t_lidar ? t_lidar : lidar;
   float* In = to_terminal && t_inertial ? t_inertial : inertial;
   float* La = to_terminal && t_last_action ? t_last_action : last_action;
-  if (L) own_sphere(c, dr, D, 0, L);
+  if (L) { own_sphere(c, dr, D, 0, L); if (E->margin_lidar) E->margin_lidar[e] = (double)sphere_margins(c, dr, D, 0, NULL, NULL, NULL); }
   if (In) inertial_obs(c, &dr[0], step, max_munition_of(c, 0), In);
   if (La) for (int k = 0; k < 4; ++k) La[k] = (float)er->last_action[k];
   /* respawn disarmed invaders (stages.py:167-174) */
@@ -1724,7 +1814,7 @@ static void stage01_step_env(ote_env* E, int e, const float* action, float* lida
   L = to_terminal && t_lidar ? t_lidar : lidar;
   In = to_terminal && t_inertial ? t_inertial : inertial;
   La = to_terminal && t_last_action ? t_last_action : last_action;
-  if (L) own_sphere(c, dr, D, 0, L);
+  if (L) { own_sphere(c, dr, D, 0, L); if (E->margin_lidar) E->margin_lidar[e] = (double)sphere_margins(c, dr, D, 0, NULL, NULL, NULL); }
   if (In) inertial_obs(c, &dr[0], er->step, 0, In);
   if (La) for (int k = 0; k < 4; ++k) La[k] = (float)er->last_action[k];
   /* replace_invader_if_close (:147-154), update_last_distance */
@@ -1779,7 +1869,7 @@ OTE_API ote_env* ote_create(const te_config* cfg) {
 OTE_API void ote_destroy(ote_env* E) {
   if (!E) return;
   free(E->drones); free(E->envs); free(E->margin); free(E->margin_state); free(E->margin_stack); free(E->ring);
-  free(E->census); free(E->census_margin); free(E);
+  free(E->census); free(E->census_margin); free(E->margin_lidar); free(E);
 }
 /* Flight census (see census_substep): on = 1 makes every later step record, per drone, the sub-step paths it took and its closest IMU
  * read to the gimbal guard; on = 0 (the default) drops the records and leaves the step with one untaken branch per sub-step. */
@@ -1802,6 +1892,23 @@ OTE_API int ote_flight_census(const ote_env* E, uint32_t* branches, double* guar
   memcpy(guard_margin, E->census_margin, n * sizeof(double));
   return 0;
 }
+/* LIDAR margins (see sphere_margins): on = 1 makes every later step / observe record how decidable the agent's tile was; off by default
+ * (ten more spherical conversions per env and step). */
+OTE_API int ote_set_lidar_margins(ote_env* E, int on) {
+  free(E->margin_lidar);
+  E->margin_lidar = NULL;
+  if (!on) return 0;
+  E->margin_lidar = (double*)malloc((size_t)E->cfg.n_envs * sizeof(double));
+  if (!E->margin_lidar) return 1;
+  for (int e = 0; e < E->cfg.n_envs; ++e) E->margin_lidar[e] = 1e30;
+  return 0;
+}
+/* out [N] f64, metres: 1e30 for an env whose last step / observe built no tile from drones (the reset observation) */
+OTE_API int ote_lidar_margins(const ote_env* E, double* out) {
+  if (!E->margin_lidar) return 1;
+  memcpy(out, E->margin_lidar, (size_t)E->cfg.n_envs * sizeof(double));
+  return 0;
+}
 OTE_API int ote_real_bytes(void) { return (int)sizeof(real); }
 OTE_API int ote_reset(ote_env* E, const uint8_t* mask) {
   for (int e = 0; e < E->cfg.n_envs; ++e) if (!mask || mask[e]) reset_env(E, e);
@@ -1817,6 +1924,7 @@ OTE_API int ote_observe(ote_env* E, float* lidar, float* inertial, float* last_a
       /* immediately after reset the Delta=1 snapshot does not exist yet: empty sphere */
       if (er->step == 0) for (int i = 0; i < lidar_words(c); ++i) L[i] = 1.0f;
       else own_sphere(c, dr, E->D, 0, L);
+      if (E->margin_lidar) E->margin_lidar[e] = er->step == 0 ? 1e30 : (double)sphere_margins(c, dr, E->D, 0, NULL, NULL, NULL);
     }
     if (inertial) inertial_obs(c, &dr[0], er->step, max_munition_of(c, 0), inertial + (size_t)e * TE_OBS_INERTIAL_WORDS);
     if (last_action) for (int k = 0; k < 4; ++k) last_action[(size_t)e * 4 + k] = (float)er->last_action[k];
@@ -1882,6 +1990,8 @@ OTE_API int ote_step(ote_env* E, const float* actions, float* lidar, float* iner
   (void)threads;
   if (E->census)
     for (size_t i = 0; i < (size_t)N * E->D; ++i) { E->census[i] = 0; E->census_margin[i] = 1e30; }
+  if (E->margin_lidar)
+    for (int e = 0; e < N; ++e) E->margin_lidar[e] = 1e30;
 #ifdef _OPENMP
 #pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
 #endif

@@ -62,6 +62,8 @@ def lib(precision: str = "f64") -> C.CDLL:
         L.ote_random_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]
         L.ote_set_flight_census.argtypes = [C.c_void_p, C.c_int]
         L.ote_flight_census.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ote_set_lidar_margins.argtypes = [C.c_void_p, C.c_int]
+        L.ote_lidar_margins.argtypes = [C.c_void_p, C.c_void_p]
         L.te_config_default.argtypes = [C.POINTER(K.Config), C.c_int32]
         L.te_quad_preset.argtypes = [C.POINTER(K.Config), C.c_int32]
         L.ote_degrees_between.restype = C.c_double
@@ -244,6 +246,18 @@ class OracleEnv:
         assert self.L.ote_flight_census(self.h, _p(branches), _p(margin)) == 0, "flight_census needs set_flight_census(True)"
         return branches, margin
 
+    def set_lidar_margins(self, on: bool = True):
+        """Record, from the next step / observe on, how decidable the agent's LIDAR tile is (lidar_margins).  Off by default."""
+        assert self.L.ote_set_lidar_margins(self.h, int(bool(on))) == 0
+
+    def lidar_margins(self) -> np.ndarray:
+        """[N] float64, metres: how far some drone of the env would have to move for the agent's tile of the last step / observe (the
+        terminal tile when one was produced) to change: the distance to the nearest cell edge, to the rim r = lidar_radius, or between
+        two ranges of one cell (own_sphere_margins).  1e30 for the reset observation."""
+        out = np.empty(self.N, np.float64)
+        assert self.L.ote_lidar_margins(self.h, _p(out)) == 0, "lidar_margins needs set_lidar_margins(True)"
+        return out
+
     def random_actions(self, seed: int, step_index: int) -> np.ndarray:
         a = np.empty((self.N, 4), np.float32)
         self.L.ote_random_actions(self.h, _p(a), seed, step_index)
@@ -367,6 +381,17 @@ def own_sphere_from_poses(pos, euler_own, own, armed, P, lidar_radius, precision
     lib(precision).ote_own_sphere_from_poses(C.c_int(len(p)), C.c_int(P), _p(p), _p(e), C.c_int(own), _p(a),
                                              C.c_double(lidar_radius), _p(sphere))
     return sphere
+
+
+def own_sphere_margins(pos, euler_own, own, armed, P, lidar_radius, precision="f64"):
+    """(cell [D] int32, rhat [D], margin [D] metres) of every other armed drone in the own sphere of `own`, in the build's arithmetic: cell =
+    theta index * 26 + phi index (-1: not a target), margin = how far the drone would have to move for the tile to change (te_oracle.c:
+    sphere_margins; 1e30 for a slot that is no target)."""
+    p = _d(pos); e = _d(euler_own); a = np.ascontiguousarray(armed, np.uint8)
+    cell = np.empty(len(p), np.int32); rhat = np.empty(len(p)); margin = np.empty(len(p))
+    lib(precision).ote_own_sphere_margins(C.c_int(len(p)), C.c_int(P), _p(p), _p(e), C.c_int(own), _p(a), C.c_double(lidar_radius),
+                                          _p(cell), _p(rhat), _p(margin))
+    return cell, rhat, margin
 
 
 def level4_position(r, min_z, u_theta, u_phi, precision="f64"):
