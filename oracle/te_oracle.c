@@ -1492,7 +1492,7 @@ static void level4_step_env(ote_env* E, int e, const float* action, float* lidar
     for (int i = 0; i < D; ++i)
       if ((S >> i) & 1u) {
         real n = norm3(dr[i].obs_pos);
-        if (i >= P) note_state_margin(mg, n, (real)c->dome_radius);
+        note_state_margin(mg, n, (real)c->dome_radius); /* (pursuers too: Level5C1's reward has no dome term that would have noted them) */
         if (n > (real)c->dome_radius) term = 1;
       }
     if (armed_pursuers == 0) term = 1;
