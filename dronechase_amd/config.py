@@ -96,6 +96,24 @@ class Config(C.Structure):
         return out
 
 
+def config_fields(cfg) -> list:
+    """[(name, value)] of every field of a te_config in declaration order, te_quad_params' as "quad.name", arrays as tuples: what two
+    configs are compared by (the struct's padding bytes say nothing)."""
+    out = []
+    for name, _ in type(cfg)._fields_:
+        v = getattr(cfg, name)
+        if isinstance(v, C.Structure):
+            out += [(f"{name}.{k}", x) for k, x in config_fields(v)]
+        else:
+            out.append((name, tuple(v) if isinstance(v, C.Array) else v))
+    return out
+
+
+def first_difference(a: Config, b: Config):
+    """The name of the first field in which two configs differ, or None."""
+    return next((name for (name, x), (_, y) in zip(config_fields(a), config_fields(b)) if x != y), None)
+
+
 def apply_overrides(cfg: Config, **kw) -> Config:
     """Set plain or `quad__field` attributes; unknown names raise (no silent typos)."""
     for k, v in kw.items():

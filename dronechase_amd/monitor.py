@@ -172,6 +172,21 @@ class EpisodeMonitor:
         for k, v in state.items():
             self._s[k][...] = v
 
+    def saved_state(self):
+        """state() as CPU tensors only, for a file read with torch.load(weights_only=True): the buffer itself, or on a CPU device every
+        numpy array as its bytes."""
+        if self.on_gpu:
+            return self.buf.cpu()
+        return {k: torch.from_numpy(np.frombuffer(v.tobytes(), dtype=np.uint8).copy()) for k, v in self._s.items()}
+
+    def load_saved_state(self, saved) -> None:
+        if self.on_gpu != torch.is_tensor(saved) or (self.on_gpu and saved.shape != self.buf.shape):
+            raise ValueError("EpisodeMonitor.load_saved_state: the state is another monitor's (its device kind, n_envs or n_records differ)")
+        if self.on_gpu:
+            self.buf.copy_(saved)
+            return
+        self.load_state({k: np.frombuffer(saved[k].numpy().tobytes(), dtype=v.dtype).reshape(v.shape) for k, v in self._s.items()})
+
 
 # ---------------------------------------------------------------------- evaluation
 DEFAULT_MAX_STEPS = 1_000_000   # see evaluate_policy

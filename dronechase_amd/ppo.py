@@ -28,13 +28,16 @@ autograd and the dense layers (rocBLAS/MIOpen): the environment side stays the H
     te_drive_wingman_bf16, the bf16 MFMA forward in front of the same clamp and drive);
   * PPOConfig.episode_stats / PPO.evaluate: episode returns, lengths and final info rows accumulated on the device (monitor.py,
     te_monitor_step), and SB3's evaluate_policy over a separate evaluation env;
+  * PPO.save / PPO.load: one torch.save file of plain data from which a run continues bit for bit on an env of the same config, or
+    fine-tunes on another task (restore_env=False); PPO.save_policy / save_sb3_policy: the weights under SB3's names, load_sb3_policy's
+    inverse; PPO.learn(callback=): the reference's evaluation, early-stop and checkpoint callbacks (callbacks.py);
   * multi-GPU: one process per GPU, each with its own env shard; gradients are averaged with
     torch.distributed all_reduce (RCCL) — the only collective of the whole system, once per minibatch.
 """
 from __future__ import annotations
 
 import copy
-from dataclasses import dataclass
+from dataclasses import asdict, dataclass, fields
 from typing import Dict, List, Optional, Tuple
 
 import ctypes as C
@@ -213,6 +216,38 @@ def load_sb3_policy(path_or_state_dict, lidar_shape=(3, 13, 26)) -> LidarInertia
             raise ValueError(f"load_sb3_policy: {back.get(name, name)!r} has shape {tuple(mapped[name].shape)}, the module's {name} {tuple(t.shape)}")
     policy.load_state_dict({k: mapped[k].float() for k in ours})
     return policy
+
+
+def _to_sb3_keys(name: str) -> List[str]:
+    """The SB3 state-dict keys of the module's parameter `name` (the inverse of _sb3_key): three for a parameter of the extractor,
+    which SB3 stores once per owner when it is shared, one for every other."""
+    if name == "log_std":
+        return [name]
+    head, _, rest = name.partition(".")
+    inv = {v: k for k, v in _SB3_EXTRACTOR.items()}
+    if head in inv:
+        return [f"{pre}features_extractor.{inv[head]}.{rest}" for pre in ("", "pi_", "vf_")]
+    return [next(pre for pre, ours in _SB3_PREFIX.items() if ours == head + ".") + rest]
+
+
+def save_sb3_policy(policy: nn.Module, path) -> None:
+    """The inverse of load_sb3_policy: a zip at `path` (a file name or a file object) whose policy.pth is the state dict of
+    `policy` (a LidarInertialActionPolicy) under SB3's MultiInputPolicy key names, the extractor three times (features_extractor,
+    pi_features_extractor, vf_features_extractor), CPU float32 tensors.  load_sb3_policy(path) gives the same parameters back, and a
+    user of the reference reads it with model.policy.load_state_dict(torch.load(policy.pth)) on a model THEY construct: this is not a
+    whole SB3 model zip (its `data` member holds cloudpickled SB3 objects, which nothing but SB3 can write).  The key names are taken
+    from SB3's documentation, as load_sb3_policy's are."""
+    import io
+    import zipfile
+    sd: Dict[str, torch.Tensor] = {}
+    for name, t in policy.state_dict().items():
+        host = t.detach().to("cpu", copy=True).contiguous()      # a bound parameter is a view of the packed buffer: no shared storage in the file
+        for key in _to_sb3_keys(name):
+            sd[key] = host
+    blob = io.BytesIO()
+    torch.save(sd, blob)
+    with zipfile.ZipFile(path, "w") as z:
+        z.writestr("policy.pth", blob.getvalue())
 
 
 GRAD_DEFAULT_ONLY = ("the gradient kernel te_policy_ppo_grad serves the default shape only (features_dim 256, net_arch (64, 64)): "
@@ -747,6 +782,99 @@ def caller_driven_pursuers(ecfg) -> List[int]:
     return [p for p in range(int(ecfg.n_pursuers)) if (int(ecfg.ally_policy) == K.ALLY_EXTERNAL and p == 1) or (mask >> p) & 1]
 
 
+CHECKPOINT_FORMAT, CHECKPOINT_VERSION = "dronechase_amd.ppo.checkpoint", 1
+# what the saved state means: a `cfg` given to PPO.load must agree with the saved one on these; every other field may differ
+RESUME_FIELDS = ("features_dim", "net_arch", "fused_optimizer", "wingman_driver", "episode_stats")
+_NO_DISTRIBUTED_CHECKPOINT = ("PPO.{}: a full checkpoint holds one rank's env shard, monitor and generators, and with more than one "
+                              "torch.distributed rank it is refused; PPO.save_policy exports the weights on any rank")
+
+
+def _host(x):
+    """Tensors to the CPU (always a copy with storage of its own: a bound parameter is a view of the whole packed buffer), through
+    dicts, lists and tuples; everything else as it is."""
+    if torch.is_tensor(x):
+        return x.detach().to("cpu", copy=True)
+    if isinstance(x, dict):
+        return {k: _host(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_host(v) for v in x)
+    return x
+
+
+def _shape_lists(shape) -> list:
+    c, features_dim, net_arch = shape
+    return [int(c), int(features_dim), [int(w) for w in net_arch]]
+
+
+def _module_of(saved: dict) -> LidarInertialActionPolicy:
+    """The CPU module of a checkpoint's {"policy_shape", "policy"} pair; a ValueError when the tensors are not that shape's."""
+    c, features_dim, net_arch = saved["policy_shape"]
+    module = LidarInertialActionPolicy(lidar_shape=(int(c), K.LIDAR_NTHETA, K.LIDAR_NPHI), features_dim=int(features_dim),
+                                       net_arch=tuple(int(w) for w in net_arch))
+    try:
+        module.load_state_dict(saved["policy"])
+    except RuntimeError as e:
+        raise ValueError(f"PPO.load: the saved weights are not those of the saved policy shape {saved['policy_shape']}: {e}") from None
+    return module
+
+
+def _load_checks(ck, env, cfg: Optional["PPOConfig"], wingman_policy, restore_env: bool, callback):
+    """Every refusal of PPO.load that needs no more than the file, the arguments and what `env` says of itself, the first that fails
+    as a ValueError; then (the config to build with, the learner's module with the saved weights on the CPU, the wingman module to
+    give the constructor or None).  Reads only: the env is not reset and nothing is allocated on its device."""
+    who = "PPO.load"
+    name = ck.get("format") if isinstance(ck, dict) else None
+    if name != CHECKPOINT_FORMAT:
+        raise ValueError(f"{who}: the file's format is {name!r}, not {CHECKPOINT_FORMAT!r}")
+    if int(ck["version"]) > CHECKPOINT_VERSION:
+        raise ValueError(f"{who}: the file is version {int(ck['version'])} of {CHECKPOINT_FORMAT}, newer than version {CHECKPOINT_VERSION}, the last this package reads")
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise ValueError(_NO_DISTRIBUTED_CHECKPOINT.format("load"))
+    known = {f.name for f in fields(PPOConfig)}
+    saved_cfg = PPOConfig(**{k: (tuple(v) if k == "net_arch" else v) for k, v in ck["cfg"].items() if k in known})
+    if cfg is None:
+        cfg = saved_cfg
+    for f in RESUME_FIELDS:
+        mine, theirs = getattr(cfg, f), getattr(saved_cfg, f)
+        if f == "net_arch":
+            mine, theirs = tuple(int(w) for w in mine), tuple(int(w) for w in theirs)
+        if mine != theirs:
+            raise ValueError(f"{who}: cfg.{f} is {mine!r}, the checkpoint was written with {theirs!r}: {', '.join(RESUME_FIELDS)} decide "
+                             "what the saved state means and cannot change")
+    policy = _module_of(ck)
+    channels = int(env.lidar.shape[1])
+    if int(ck["policy_shape"][0]) != channels:
+        raise ValueError(f"{who}: the saved policy reads {int(ck['policy_shape'][0])} LIDAR channels, the environment has {channels}")
+    ecfg = getattr(env, "cfg", None)
+    if restore_env:
+        if ck["env_state"] is None or ck["env_config"] is None:
+            raise ValueError(f"{who}: the checkpoint holds no env state (its env had none to give): pass restore_env=False")
+        abi = int(_lib.load().te_abi_version())
+        if int(ck["abi_version"]) != abi:
+            raise ValueError(f"{who}: the env state was written under ABI version {int(ck['abi_version'])}, the library's is {abi}: "
+                             "restore_env=False takes the learner alone")
+        if ecfg is None or not hasattr(env, "set_state"):
+            raise ValueError(f"{who}: restore_env=True needs an env with a config and set_state")
+        saved_bytes = ck["env_config"].numpy().tobytes()
+        if saved_bytes != bytes(ecfg):
+            if len(saved_bytes) != C.sizeof(K.Config):
+                raise ValueError(f"{who}: the saved env config has te_config.struct_size {len(saved_bytes)}, this library's is {C.sizeof(K.Config)}")
+            theirs = K.Config.from_buffer_copy(saved_bytes)
+            field = K.first_difference(theirs, ecfg)
+            if field is not None:
+                values = dict(K.config_fields(theirs))[field], dict(K.config_fields(ecfg))[field]
+                raise ValueError(f"{who}: the env's te_config.{field} is {values[1]!r}, the checkpoint's env had {values[0]!r}: restore_env=True "
+                                 "continues the saved env, restore_env=False takes the learner alone")
+    if callback is not None:
+        if ck["callbacks"] is None:
+            raise ValueError(f"{who}: a callback was given, but the checkpoint holds no callback state (learn() had none when it was saved)")
+        callback.check_state(ck["callbacks"])
+    saved = ck["wingman"]
+    if wingman_policy is None and saved is not None and not saved["snapshot"] and caller_driven_pursuers(ecfg):
+        wingman_policy = _module_of(saved).requires_grad_(False)     # the frozen module the saved run was given
+    return cfg, policy, wingman_policy
+
+
 LOSS_KEYS = ("pg_loss", "v_loss", "entropy", "clip_frac")        # update()'s log, in the order of te_policy_ppo_grad's stats_out
 EV_KEYS = ("adv_mean", "adv_std", "ret_mean", "ret_std")         # PPO._ev_stats: read with the log, folded into "explained_variance"
 
@@ -825,6 +953,8 @@ class PPO:
             from .monitor import EpisodeMonitor
             self.monitor = EpisodeMonitor(env.N, self.device, n_records=0)
         self.num_timesteps = 0
+        self._rollout_pending = False  # collect() filled the buffer and update() has not consumed it: the one state save() refuses
+        self._callback = None          # the callback learn() was last given: save() stores its state
 
     def _refusal(self, wingman_given: bool) -> Optional[str]:
         """Why this config, env and policy module cannot be trained together (the ValueError's text), or None: every rule that needs
@@ -968,9 +1098,9 @@ class PPO:
             self.sync_wingmen()
         if self._obs is None:
             self._obs = dict(zip(("lidar", "inertial_data", "last_action"), self.env.observe()))
-        if self.cfg.use_graph and self.device.type == "cuda":
-            return self._collect_graph()
-        return self._collect_eager()
+        out = self._collect_graph() if self.cfg.use_graph and self.device.type == "cuda" else self._collect_eager()
+        self._rollout_pending = True
+        return out
 
     @torch.no_grad()
     def _collect_eager(self) -> Dict[str, float]:
@@ -1083,6 +1213,7 @@ class PPO:
             keys, means = keys + EV_KEYS, torch.cat((means, self._ev_stats))
         out = dict(zip(keys, means.tolist()))      # the one host read
         self._updates_since_sync += 1
+        self._rollout_pending = False
         if c.fused_advantages:          # ret - values is the advantage: 1 - Var(adv) / Var(ret), SB3's explained_variance
             _, std_adv, _, std_ret = (out.pop(k) for k in EV_KEYS)
             out["explained_variance"] = float("nan") if std_ret == 0.0 else 1.0 - (std_adv * std_adv) / (std_ret * std_ret)
@@ -1120,10 +1251,126 @@ class PPO:
                                  self._flat_grad, self._grad_stats)
         self._step()
 
-    def learn(self, total_timesteps: int, log=None):
+    def learn(self, total_timesteps: int, log=None, callback=None):
+        """collect() and update() until num_timesteps reaches total_timesteps.  callback (callbacks.py: a BaseCallback, usually a
+        CallbackList) is consulted once per iteration, after update() and after log: when it returns False, learn returns."""
+        if callback is not None:
+            callback.init_callback(self)
+            self._callback = callback
         while self.num_timesteps < total_timesteps:
             r = self.collect()
             u = self.update()
             if log:
                 log({**r, **u, "timesteps": self.num_timesteps})
+            if callback is not None and callback.on_iteration() is False:
+                break
         return self
+
+    # ------------------------------------------------------------------ save, resume, export
+    def save_policy(self, path) -> None:
+        """The learner's weights as an SB3-named policy zip (save_sb3_policy); works on any torch.distributed rank."""
+        save_sb3_policy(self.policy, path)
+
+    def save(self, path) -> None:
+        """Everything the next collect() and update() read, as one torch.save file of CPU tensors, numbers, strings, lists and dicts
+        (PPO.load reads it with weights_only=True): the config, the policy's shape and weights, the optimiser's state, num_timesteps,
+        the wingman driver's frozen weights and the count of updates since their last sync, the observation the next rollout starts
+        from, the env's config and state blob, the episode monitor, both torch generators and the state of learn()'s callback.  The
+        rollout buffer is not saved: legal before the first collect() and between update() and the next collect(); with a collected
+        rollout that update() has not consumed it is a ValueError and nothing is written.  Derived buffers (the packed fp32 copy, the
+        bf16 weights and their transposes, the wingman's) are not saved: load() repacks them from the fp32 weights, which reproduces
+        them bit for bit."""
+        if self._rollout_pending:
+            raise ValueError("PPO.save: collect() has filled a rollout that update() has not consumed, and the rollout buffer is not "
+                             "part of a checkpoint: save between update() and the next collect()")
+        if self.distributed:
+            raise ValueError(_NO_DISTRIBUTED_CHECKPOINT.format("save"))
+        torch.save(self._checkpoint(), path)
+
+    def _checkpoint(self) -> dict:
+        env, dev = self.env, self.device
+        ecfg = getattr(env, "cfg", None)
+        packed = isinstance(self.opt, PackedAdam)
+        wingman = None
+        if self.wingman is not None:
+            wingman = {"policy_shape": _shape_lists(policy_shape(self.wingman.policy)), "policy": _host(self.wingman.policy.state_dict()),
+                       "snapshot": bool(self._wingman_snapshot)}
+        return {
+            "format": CHECKPOINT_FORMAT, "version": CHECKPOINT_VERSION, "abi_version": int(_lib.load().te_abi_version()),
+            "cfg": {**asdict(self.cfg), "net_arch": [int(w) for w in self.cfg.net_arch]},
+            "policy_shape": _shape_lists(policy_shape(self.policy)), "policy": _host(self.policy.state_dict()),
+            "optimizer_kind": "PackedAdam" if packed else "Adam", "optimizer": _host(self.opt.state_dict()),
+            "num_timesteps": int(self.num_timesteps), "updates_since_sync": int(self._updates_since_sync), "wingman": wingman,
+            "obs": None if self._obs is None else _host(dict(self._obs)),
+            "env_config": None if ecfg is None else torch.frombuffer(bytearray(bytes(ecfg)), dtype=torch.uint8),
+            "env_state": _host(env.get_state()) if hasattr(env, "get_state") else None,
+            "monitor": None if self.monitor is None else self.monitor.saved_state(),
+            "cpu_rng_state": torch.get_rng_state(),
+            "cuda_rng_state": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None,
+            "callbacks": None if self._callback is None else self._callback.state_dict(),
+        }
+
+    @classmethod
+    def load(cls, path, env, cfg: Optional[PPOConfig] = None, wingman_policy: Optional[nn.Module] = None, restore_env: bool = True,
+             callback=None) -> "PPO":
+        """The PPO that save() wrote, on `env`: read with torch.load(weights_only=True), built from the saved config (or `cfg`, which
+        must agree with it on RESUME_FIELDS and may differ in everything else: a new learning rate, batch size or n_steps), then restored.
+        restore_env=True: `env` must have the saved env's config (a ValueError names the first te_config field that differs); its state,
+        the next rollout's observation, the episode monitor and both torch generators are restored, and learn() continues bit for bit
+        as the saved run would have.  With use_graph the rollout step is captured here, BEFORE the generators are restored: the capture
+        draws three times, which the saved run did before its first rollout.
+        restore_env=False: the learner, the optimiser, num_timesteps and the wingman's weights are taken and the env is left freshly
+        reset: the reference's stage03 continuing from a stage02 model (another task, the same observation shape).  No generator is
+        restored then: the CPU generator is left as every PPO(...) leaves it (the constructor seeds it, here with 0).
+        wingman_policy: flies the caller-driven pursuers as given, in place of the saved weights; without it a snapshot driver flies
+        the saved frozen weights (NOT the learner's: the next sync comes when the saved count says so), and a driver that was given
+        as a module is rebuilt from the file.  callback: a callback of the classes, in the order, of the one whose state the file
+        holds; its state is restored, and it is what learn() should be given.
+        Every refusal is a ValueError raised before the env is reset and before anything is allocated on its device."""
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        given = wingman_policy is not None
+        cfg, policy, wingman_policy = _load_checks(ck, env, cfg, wingman_policy, restore_env, callback)
+        probe = cls.__new__(cls)        # the constructor's own refusals, asked before a wingman module is moved to the env's device
+        probe.cfg, probe.device, probe.wingmen, probe.policy = cfg, env.device, caller_driven_pursuers(getattr(env, "cfg", None)), policy
+        refusal = probe._refusal(wingman_policy is not None)
+        if refusal:
+            raise ValueError(refusal)
+        if wingman_policy is not None and not given:        # rebuilt from the file, on the CPU
+            wingman_policy = wingman_policy.to(env.device)
+        self = cls(env, cfg, policy=policy, seed=0, wingman_policy=wingman_policy)
+        self._restore(ck, restore_env)
+        if callback is not None:
+            callback.load_state_dict(ck["callbacks"])
+            self._callback = callback
+        return self
+
+    @torch.no_grad()
+    def _restore(self, ck: dict, restore_env: bool) -> None:
+        """The constructor was given the saved weights as its policy module, so the packed buffer, the bound parameters and the bf16
+        copies already hold them.  Here: the optimiser, the counters, the wingman's frozen weights, and with restore_env the env."""
+        dev = self.device
+        if isinstance(self.opt, PackedAdam):
+            self.opt.load_state_dict(ck["optimizer"])
+        else:       # the state only: the hyper-parameters are this config's (a new learning rate is a reason to pass cfg)
+            self.opt.load_state_dict({"state": ck["optimizer"]["state"], "param_groups": self.opt.state_dict()["param_groups"]})
+        self.num_timesteps = int(ck["num_timesteps"])
+        saved = ck["wingman"]
+        if self._wingman_snapshot:
+            if saved is not None and saved["snapshot"]:     # the frozen weights as they were: no sync, the saved count decides the next one
+                self.wingman.load_from(_module_of(saved).to(dev))
+                self._updates_since_sync = int(ck["updates_since_sync"])
+            else:                                           # the saved run had no snapshot to keep: start from the restored learner
+                self.sync_wingmen()
+        if not restore_env:
+            return
+        self.env.set_state(ck["env_state"])
+        if ck["obs"] is not None:
+            self._obs = {k: ck["obs"][k].to(dev) for k in ("lidar", "inertial_data", "last_action")}
+            if self.cfg.use_graph and dev.type == "cuda":
+                self._capture_step()        # leaves the env state and _g_obs as they were given; draws from the CUDA generator
+                self._obs = self._g_obs     # as after every graph collect(): the next rollout reads the static tensors
+        if self.monitor is not None:
+            self.monitor.load_saved_state(ck["monitor"])
+        torch.set_rng_state(ck["cpu_rng_state"])
+        if dev.type == "cuda":
+            torch.cuda.set_rng_state(ck["cuda_rng_state"], dev)
