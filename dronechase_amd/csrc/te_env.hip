@@ -46,6 +46,7 @@
 #include "te_engage_slots.hpp"
 #include "te_policy.hpp"
 #include "te_policy_bf16.hpp"
+#include "te_sphere.hpp"
 #include "te_wingman.hpp"
 #include "te_policy_grad.hpp"
 #include "te_policy_grad_bf16.hpp"
@@ -2171,6 +2172,47 @@ __attribute__((visibility("default"))) int te_policy_adam_step_bf16(float* param
   if (policy_adam_check("te_policy_adam_step_bf16", c) || policy_repack_check("te_policy_adam_step_bf16", weights_bf16, weights_bf16_t)) return 1;
   const OptRepack repack = policy_repack_plan(s, weights_bf16, weights_bf16_t);
   return policy_adam_launch(c, &repack, stream);
+}
+
+// ---- the level5 student's sphere encoder (te_sphere.hpp): every check is on the host, before any launch
+static int sphere_channels_check(const std::string& who, int32_t channels) {
+  if (channels != 3) return fail(who + ": channels must be 3 (the stacked observation's), not " + std::to_string(channels));
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_sphere_encode_param_words(int32_t channels, size_t* out_words) {
+  if (!out_words) return fail("te_sphere_encode_param_words: null argument out_words");
+  if (sphere_channels_check("te_sphere_encode_param_words", channels)) return 1;
+  *out_words = (size_t)sph_layout(3).words;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_sphere_encode(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres,
+                                                            const float* stacked, const uint8_t* mask, float* out, void* stream) {
+  const std::string who = "te_sphere_encode";
+  if (sphere_channels_check(who, channels)) return 1;
+  if (n_spheres < 1 || n_spheres > kSphMaxSpheres)
+    return fail(who + ": n_spheres must be in 1 .. " + std::to_string(kSphMaxSpheres) + ", not " + std::to_string(n_spheres));
+  if (n_rows < 1) return fail(who + ": n_rows must be positive, not " + std::to_string(n_rows));
+  if ((int64_t)n_rows * n_spheres > INT32_MAX) return fail(who + ": n_rows * n_spheres must be at most 2^31 - 1");
+  const std::pair<const char*, const void*> required[] = {{"params", params}, {"stacked", stacked}, {"out", out}};
+  for (const auto& [name, q] : required) {
+    if (!q) return fail(who + ": null argument " + name);
+    if ((uintptr_t)q & 15) return fail(who + ": " + name + " must be 16-byte aligned");
+  }
+  // persistent workgroups, one per CU at most: each stages the weights into LDS once and strides over the spheres
+  static int cus[64];
+  int dev = 0;
+  TE_HIP(hipGetDevice(&dev));
+  int n_cu = dev < 64 ? cus[dev] : 0;
+  if (!n_cu) {
+    TE_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    if (n_cu < 1) return fail(who + ": the device reports no compute units");
+    if (dev < 64) cus[dev] = n_cu;
+  }
+  const int total = n_rows * n_spheres;
+  const SphereIO io{params, stacked, mask, out, n_spheres, total};
+  return policy_launch(&sphere_encode_kernel<3>, PolGeom{1, kSphThreads, sph_lds_plan(3).words * 4}, std::min(total, n_cu), stream, io);
 }
 
 // ---- advantage estimation (te_rollout.hpp): every check is on the host, before any launch

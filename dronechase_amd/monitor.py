@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import config as K
 
 INFO_MEAN_KEYS = ("ep_agent_kills_mean", "ep_allies_kills_mean", "ep_deads_mean", "ep_wave_mean")   # info[0..3], vec_env.INFO_KEYS
 
@@ -192,10 +193,25 @@ class EpisodeMonitor:
 DEFAULT_MAX_STEPS = 1_000_000   # see evaluate_policy
 
 
-def _actor(policy, deterministic: bool):
+STACKED_KEYS = ("stacked_spheres", "validity_mask", "inertial_data", "last_action")   # step_stacked's order, student.OBS_KEYS
+STACKED_NEEDS_STUDENT = ("evaluate_policy: this environment gives the stacked (level5) observation: the policy that fits is a "
+                         "dronechase_amd.student.FLIAStudent or a StudentDriver around one")
+STUDENT_NEEDS_STACKED = ("evaluate_policy: a FLIAStudent / StudentDriver reads the stacked (level5) observation, which this environment "
+                         "does not give: the policy that fits is a LidarInertialActionPolicy, a FusedPolicy, a PolicyDriver or a PPO")
+
+
+def _actor(policy, deterministic: bool, stacked: bool = False):
     """obs dict -> clamped actions [N, 4], for every kind of policy evaluate_policy takes."""
     from .ppo import PPO, FusedPolicy, PolicyDriver
+    from .student import FLIAStudent, StudentDriver
 
+    if isinstance(policy, FLIAStudent):
+        policy = StudentDriver(policy, fused_encoder=False)
+    if isinstance(policy, StudentDriver) != stacked:
+        raise ValueError(STACKED_NEEDS_STUDENT if stacked else STUDENT_NEEDS_STACKED)
+    if stacked:
+        policy.refresh()
+        return lambda obs: policy.predict(obs, deterministic=deterministic)[0]
     if isinstance(policy, PPO):
         policy = policy.fused if policy.fused is not None else policy.policy
     if isinstance(policy, FusedPolicy):
@@ -233,6 +249,12 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 100, deterministic: bool
     pursuer before every step, as PPO's rollout does.  A FusedPolicy is passed through as it is, so the drive's precision follows the
     object: FusedPolicy(module, precision="bf16"), or the wingman of a PPO with PPOConfig.wingman_bf16, flies through te_drive_wingman_bf16;
     a module is packed in fp32.
+    On an env that gives the stacked observation (cfg.stacked_obs: level5, level5_fusion, level5_c1) `policy` is a
+    student.FLIAStudent (flown as StudentDriver(policy, fused_encoder=False)) or a StudentDriver (refreshed once, before the first
+    step); the loop steps with step_stacked and feeds the four level5 keys, everything else is the same.  Any other policy there,
+    and a student on any other env, is a ValueError that says which policy fits; the all-scripted tasks (level5_dumb, level5_2bt,
+    cfg.agent_scripted / cfg.evaluation on a stacked env) have no agent to fly and are refused by name.  The student has no
+    distribution: deterministic=False is StudentDriver's ValueError.
     The host reads 4 bytes (the number of recorded episodes) every `poll_every` steps and never per step; steps taken after
     the last quota is met change nothing.  max_steps bounds the loop: if it is reached with fewer than n_eval_episodes recorded,
     RuntimeError says how many were.  Default 1 000 000 steps, far more than any task's episodes need (a stage03 episode is at most a
@@ -245,8 +267,12 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 100, deterministic: bool
         raise ValueError("evaluate_policy: n_eval_episodes and poll_every must be positive")
     max_steps = DEFAULT_MAX_STEPS if max_steps is None else int(max_steps)
     cfg = getattr(backend, "cfg", None)
-    if cfg is not None and bool(getattr(cfg, "stacked_obs", 0)):
-        raise ValueError("evaluate_policy: the stacked (level5) observation has no policy in this package")
+    stacked = cfg is not None and bool(getattr(cfg, "stacked_obs", 0))
+    if stacked and (getattr(cfg, "agent_scripted", 0) or getattr(cfg, "evaluation", 0)):
+        name = next((k for k, v in K.TASKS.items() if v == int(cfg.task)), str(int(cfg.task)))
+        why = "agent_scripted" if cfg.agent_scripted else "evaluation"
+        raise ValueError(f"evaluate_policy: task {name!r} has no agent for a policy to fly (cfg.{why} is set: every pursuer is scripted); "
+                         "level5, level5_fusion and level5_c1 have one")
     wingmen = caller_driven_pursuers(cfg)
     if wingmen:
         if wingman_policy is None and isinstance(policy, PPO):
@@ -255,20 +281,23 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 100, deterministic: bool
             raise ValueError("evaluate_policy: this environment has caller-driven pursuers (exp05's ally, the evaluation driver mask): pass wingman_policy")
         wingman = wingman_policy if isinstance(wingman_policy, FusedPolicy) else FusedPolicy(wingman_policy)
         wingman.refresh()
-    act = _actor(policy, deterministic)
+    act = _actor(policy, deterministic, stacked)
     obs = backend.reset()
+    if stacked:         # reset returns the own-sphere observation on the tasks te_observe serves
+        obs = backend.observe_stacked()
     if obs is None:
         raise ValueError("evaluate_policy: this environment's reset returns no observation")
     monitor = EpisodeMonitor(backend.N, backend.device, n_records=n)
-    keys = ("lidar", "inertial_data", "last_action")
+    keys = STACKED_KEYS if stacked else ("lidar", "inertial_data", "last_action")
+    step = backend.step_stacked if stacked else backend.step
     steps, recorded = 0, 0
     while recorded < n:
         if steps >= max_steps:
             raise RuntimeError(f"evaluate_policy: {recorded} of {n} episodes recorded after max_steps = {max_steps} steps")
-        a = act(dict(zip(keys, obs[:3]))).contiguous()
+        a = act(dict(zip(keys, obs[:len(keys)]))).contiguous()
         for w in wingmen:
             backend.drive_wingman(w, wingman)
-        *obs, reward, done, info = backend.step(a, terminal=False)
+        *obs, reward, done, info = step(a, terminal=False)
         monitor.step(reward, done, info)
         steps += 1
         if steps % poll_every == 0 or steps >= max_steps:

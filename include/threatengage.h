@@ -774,6 +774,33 @@ int te_monitor_step(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, 
 int te_monitor_stats(void* mon, size_t bytes, int32_t n_envs, int32_t n_records, te_monitor_summary* out, int32_t reset_window,
                      void* stream);
 
+/* Sphere encoder of the level5 student (dronechase_amd/student.py): the two convolution blocks of the reference's SphereCNN
+ * (fused_lidar_extractor.py:653-720) over the stacked observation, skipping the spheres the network never looks at.  fp32 on
+ * v_mfma_f32_16x16x4_f32 (dronechase_amd/csrc/te_sphere.hpp); inference only, no backward.
+ *
+ * params (16-byte aligned, te_sphere_encode_param_words(channels) floats) holds the reference's four tensors, each flattened, in this
+ * order: conv1 w[32][C][5][5], b[32], conv2 w[64][32][3][3], b[64].
+ *
+ * Per sphere x [C][13][26]:  block1 = circular padding by 2 in W, constant padding by 2 in H with the value 1.0 (the LIDAR's "no
+ * data"), conv 5x5 stride 2, ReLU -> [32][7][13];  block2 = circular padding by 1 in W, constant 1.0 padding by 1 in H (on the feature
+ * map too), conv 3x3 stride 2, ReLU -> [64][4][7];  out = its 1792 values in (co, oh, ow) order.  The Linear(1792, 512) behind them
+ * is not part of the call.
+ *
+ * stacked [n_rows][n_spheres][C][13][26] f32, mask [n_rows][n_spheres] u8 or NULL, out [n_rows][n_spheres][1792] f32, stacked and out
+ * 16-byte aligned.  Sphere s of row r COUNTS iff mask == NULL, or mask[r][s] != 0, or s == 0 and the row's mask is all zero (the
+ * attention gives every other sphere the weight 0, and MLPomega._grant_at_least_one_valid turns sphere 0 of an all-zero row on).  A
+ * sphere that counts gets its features; one that does not gets exact zeros and its input is never read (it may hold anything, NaN
+ * included).
+ *
+ * Served: channels == 3, 1 <= n_spheres <= 8, n_rows >= 1, n_rows * n_spheres <= 2^31 - 1.  Any other value, a NULL pointer other
+ * than mask, or a misaligned pointer is refused with te_last_error text that names the argument, before anything is launched.  The
+ * call enqueues one launch on `stream` of the current device: no allocation and no host synchronisation, so a HIP graph can capture
+ * it.  An element's sum order is fixed (bias first, then k): a sphere's features are bitwise the same whatever its row, its slot,
+ * n_rows or the mask of other spheres. */
+int te_sphere_encode_param_words(int32_t channels, size_t* out_words);
+int te_sphere_encode(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres, const float* stacked,
+                     const uint8_t* mask, float* out, void* stream);
+
 int te_abi_version(void);
 const char* te_last_error(void);
 
