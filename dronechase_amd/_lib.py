@@ -25,7 +25,7 @@ EXPORTS = (
     "te_policy_opt_state_bytes", "te_policy_adam_step", "te_policy_adam_step_bf16", "te_policy_ppo_epoch",
     "te_rollout_gae", "te_adv_stats_workspace_bytes", "te_adv_stats",
     "te_monitor_bytes", "te_monitor_layout", "te_monitor_init", "te_monitor_step", "te_monitor_stats",
-    "te_sphere_encode_param_words", "te_sphere_encode",
+    "te_sphere_encode_param_words", "te_sphere_encode", "te_sphere_encode_grad_workspace_bytes", "te_sphere_encode_grad",
 )
 
 
@@ -136,6 +136,8 @@ def load() -> C.CDLL:
     L.te_monitor_stats.argtypes = mon + [vp, i32, vp]
     L.te_sphere_encode_param_words.argtypes = [i32, C.POINTER(C.c_size_t)]
     L.te_sphere_encode.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+    L.te_sphere_encode_grad_workspace_bytes.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
+    L.te_sphere_encode_grad.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     if L.te_abi_version() != K.TE_ABI_VERSION:
         raise RuntimeError("libthreatengage.so ABI version differs from dronechase_amd.config")
     _LIB = L

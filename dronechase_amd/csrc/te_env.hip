@@ -1081,7 +1081,7 @@ struct PolArg { using type = T; };   // the arguments convert to the kernel's fo
 
 template <class... Args>
 static int policy_launch(void (*fn)(Args...), PolGeom geom, int rows, void* stream, const typename PolArg<Args>::type&... args) {
-  if (policy_opt_in(reinterpret_cast<const void*>(fn), geom.lds_bytes)) return 1;
+  if (geom.lds_bytes && policy_opt_in(reinterpret_cast<const void*>(fn), geom.lds_bytes)) return 1;   // no dynamic LDS: nothing to opt in to
   const dim3 grid((unsigned)((rows + geom.M - 1) / geom.M));
   hipLaunchKernelGGL(fn, grid, dim3(geom.threads), (size_t)geom.lds_bytes, (hipStream_t)stream, args...);
   TE_HIP(hipGetLastError());
@@ -2187,20 +2187,26 @@ __attribute__((visibility("default"))) int te_sphere_encode_param_words(int32_t 
   return 0;
 }
 
-__attribute__((visibility("default"))) int te_sphere_encode(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres,
-                                                            const float* stacked, const uint8_t* mask, float* out, void* stream) {
-  const std::string who = "te_sphere_encode";
+// the domain both sphere calls serve
+static int sphere_domain_check(const std::string& who, int32_t channels, int32_t n_rows, int32_t n_spheres) {
   if (sphere_channels_check(who, channels)) return 1;
   if (n_spheres < 1 || n_spheres > kSphMaxSpheres)
     return fail(who + ": n_spheres must be in 1 .. " + std::to_string(kSphMaxSpheres) + ", not " + std::to_string(n_spheres));
   if (n_rows < 1) return fail(who + ": n_rows must be positive, not " + std::to_string(n_rows));
   if ((int64_t)n_rows * n_spheres > INT32_MAX) return fail(who + ": n_rows * n_spheres must be at most 2^31 - 1");
-  const std::pair<const char*, const void*> required[] = {{"params", params}, {"stacked", stacked}, {"out", out}};
+  return 0;
+}
+
+static int sphere_pointers_check(const std::string& who, std::initializer_list<std::pair<const char*, const void*>> required) {
   for (const auto& [name, q] : required) {
     if (!q) return fail(who + ": null argument " + name);
-    if ((uintptr_t)q & 15) return fail(who + ": " + name + " must be 16-byte aligned");
+    if ((uintptr_t)q & 15) return fail(who + ": " + std::string(name) + " must be 16-byte aligned");
   }
-  // persistent workgroups, one per CU at most: each stages the weights into LDS once and strides over the spheres
+  return 0;
+}
+
+// the compute units of the current device, asked once per device: the sphere kernels run persistent workgroups, one per CU at most
+static int sphere_cu_count(const std::string& who, int* out) {
   static int cus[64];
   int dev = 0;
   TE_HIP(hipGetDevice(&dev));
@@ -2210,9 +2216,58 @@ __attribute__((visibility("default"))) int te_sphere_encode(const float* params,
     if (n_cu < 1) return fail(who + ": the device reports no compute units");
     if (dev < 64) cus[dev] = n_cu;
   }
+  *out = n_cu;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_sphere_encode(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres,
+                                                            const float* stacked, const uint8_t* mask, float* out, void* stream) {
+  const std::string who = "te_sphere_encode";
+  if (sphere_domain_check(who, channels, n_rows, n_spheres)) return 1;
+  if (sphere_pointers_check(who, {{"params", params}, {"stacked", stacked}, {"out", out}})) return 1;
+  // persistent workgroups: each stages the weights into LDS once and strides over the spheres
+  int n_cu = 0;
+  if (sphere_cu_count(who, &n_cu)) return 1;
   const int total = n_rows * n_spheres;
   const SphereIO io{params, stacked, mask, out, n_spheres, total};
   return policy_launch(&sphere_encode_kernel<3>, PolGeom{1, kSphThreads, sph_lds_plan(3).words * 4}, std::min(total, n_cu), stream, io);
+}
+
+// The workspace of te_sphere_encode_grad: one partial gradient per workgroup the call can launch.  The bound on the grid does not
+// depend on the device, so the size can be asked (and a short workspace refused) without one.
+static size_t sphere_grad_workspace(int32_t n_rows, int32_t n_spheres) {
+  const size_t groups = (size_t)std::min<int64_t>((int64_t)n_rows * n_spheres, kSphGradMaxGroups);
+  return (groups * sph_layout(3).words * sizeof(float) + 255) / 256 * 256;
+}
+
+__attribute__((visibility("default"))) int te_sphere_encode_grad_workspace_bytes(int32_t channels, int32_t n_rows, int32_t n_spheres,
+                                                                                 size_t* out_bytes) {
+  const std::string who = "te_sphere_encode_grad_workspace_bytes";
+  if (!out_bytes) return fail(who + ": null argument out_bytes");
+  if (sphere_domain_check(who, channels, n_rows, n_spheres)) return 1;
+  *out_bytes = sphere_grad_workspace(n_rows, n_spheres);
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_sphere_encode_grad(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres,
+                                                                 const float* stacked, const uint8_t* mask, const float* out,
+                                                                 const float* d_out, float* grad, void* workspace, size_t workspace_bytes,
+                                                                 void* stream) {
+  const std::string who = "te_sphere_encode_grad";
+  if (sphere_domain_check(who, channels, n_rows, n_spheres)) return 1;
+  if (sphere_pointers_check(who, {{"params", params}, {"stacked", stacked}, {"out", out}, {"d_out", d_out}, {"grad", grad}})) return 1;
+  if (!workspace) return fail(who + ": null argument workspace");
+  if ((uintptr_t)workspace & 255) return fail(who + ": workspace must be 256-byte aligned");
+  const size_t need = sphere_grad_workspace(n_rows, n_spheres);
+  if (workspace_bytes < need)
+    return fail(who + ": workspace too small (" + std::to_string(workspace_bytes) + " bytes, te_sphere_encode_grad_workspace_bytes says " +
+                std::to_string(need) + ")");
+  int n_cu = 0;
+  if (sphere_cu_count(who, &n_cu)) return 1;
+  const int total = n_rows * n_spheres, groups = std::min({total, n_cu, kSphGradMaxGroups}), words = sph_layout(3).words;
+  const SphereGradIO io{params, stacked, mask, out, d_out, static_cast<float*>(workspace), n_spheres, total};
+  if (policy_launch(&sphere_encode_grad_kernel<3>, PolGeom{1, kSphThreads, sph_grad_lds_plan(3).words * 4}, groups, stream, io)) return 1;
+  return policy_launch(&sphere_grad_reduce_kernel, PolGeom{256, 256, 0}, words, stream, static_cast<const float*>(workspace), groups, words, grad);
 }
 
 // ---- advantage estimation (te_rollout.hpp): every check is on the host, before any launch

@@ -776,7 +776,8 @@ int te_monitor_stats(void* mon, size_t bytes, int32_t n_envs, int32_t n_records,
 
 /* Sphere encoder of the level5 student (dronechase_amd/student.py): the two convolution blocks of the reference's SphereCNN
  * (fused_lidar_extractor.py:653-720) over the stacked observation, skipping the spheres the network never looks at.  fp32 on
- * v_mfma_f32_16x16x4_f32 (dronechase_amd/csrc/te_sphere.hpp); inference only, no backward.
+ * v_mfma_f32_16x16x4_f32 (dronechase_amd/csrc/te_sphere.hpp).  te_sphere_encode is the forward; te_sphere_encode_grad, below, is the
+ * gradient of its parameters.
  *
  * params (16-byte aligned, te_sphere_encode_param_words(channels) floats) holds the reference's four tensors, each flattened, in this
  * order: conv1 w[32][C][5][5], b[32], conv2 w[64][32][3][3], b[64].
@@ -800,6 +801,28 @@ int te_monitor_stats(void* mon, size_t bytes, int32_t n_envs, int32_t n_records,
 int te_sphere_encode_param_words(int32_t channels, size_t* out_words);
 int te_sphere_encode(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres, const float* stacked,
                      const uint8_t* mask, float* out, void* stream);
+
+/* The backward of te_sphere_encode with respect to its parameters: grad (te_sphere_encode_param_words(channels) floats, in params'
+ * layout) = sum over the counting spheres of d(out) / d(params) applied to d_out.  No gradient with respect to `stacked` exists: it is
+ * an observation.
+ *
+ * params, channels, n_rows, n_spheres, stacked and mask as te_sphere_encode took them; out [n_rows][n_spheres][1792] is what that call
+ * wrote (its sign pattern is block2's ReLU mask, so the mask is the forward's own decision); d_out, of out's shape, is the upstream
+ * gradient.  Block1's activations are recomputed from `stacked` by the forward's own code, bitwise as the forward had them.  A sphere
+ * that does not count contributes nothing, and its stacked, out and d_out entries are never read (they may hold NaN).
+ *
+ * workspace: 256-byte aligned, at least te_sphere_encode_grad_workspace_bytes(channels, n_rows, n_spheres) bytes, its content
+ * irrelevant; each workgroup leaves one partial gradient there and a second launch sums the partials in workgroup order into grad,
+ * which is overwritten, not accumulated into.  There are no float atomics: the same arguments on the same device give the same bits
+ * on every call.  Against a float64 reference the result differs as float32 sums of up to n_rows * n_spheres * 91 terms do.
+ *
+ * Served: te_sphere_encode's domain.  A value outside it, a NULL pointer other than mask, params / stacked / out / d_out / grad not
+ * 16-byte aligned, or a workspace that is misaligned or too short is refused with te_last_error text that names the argument, before
+ * anything is launched.  Two launches on `stream` of the current device, no allocation and no host synchronisation. */
+int te_sphere_encode_grad_workspace_bytes(int32_t channels, int32_t n_rows, int32_t n_spheres, size_t* out_bytes);
+int te_sphere_encode_grad(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres, const float* stacked,
+                          const uint8_t* mask, const float* out, const float* d_out, float* grad, void* workspace,
+                          size_t workspace_bytes, void* stream);
 
 int te_abi_version(void);
 const char* te_last_error(void);
