@@ -26,6 +26,7 @@ EXPORTS = (
     "te_rollout_gae", "te_adv_stats_workspace_bytes", "te_adv_stats",
     "te_monitor_bytes", "te_monitor_layout", "te_monitor_init", "te_monitor_step", "te_monitor_stats",
     "te_sphere_encode_param_words", "te_sphere_encode", "te_sphere_encode_grad_workspace_bytes", "te_sphere_encode_grad",
+    "te_dataset_layout", "te_dataset_init", "te_dataset_append", "te_dataset_gather",
 )
 
 
@@ -36,6 +37,16 @@ class TEError(RuntimeError):
 class MonitorOffsets(C.Structure):
     """te_monitor_offsets: byte offsets of the arrays inside an episode-monitor buffer (include/threatengage.h)."""
     _fields_ = [(n, C.c_size_t) for n in ("bytes", "n_rows", "rows", "ret", "len", "episodes", "last_ret", "last_len", "rec_info", "rec_ret", "rec_len")]
+
+
+class DatasetGeom(C.Structure):
+    """te_dataset_geom: the shape of an imitation dataset (include/threatengage.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("capacity", "max_append_rows", "n_spheres", "channels")]
+
+
+class DatasetOffsets(C.Structure):
+    """te_dataset_offsets: byte offsets of the header, the append scratch and the rings inside a dataset buffer (include/threatengage.h)."""
+    _fields_ = [(n, C.c_size_t) for n in ("bytes", "header", "dst", "stacked", "mask", "inertial", "last_action", "teacher")]
 
 
 class PolicyShape(C.Structure):
@@ -138,6 +149,11 @@ def load() -> C.CDLL:
     L.te_sphere_encode.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.te_sphere_encode_grad_workspace_bytes.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
     L.te_sphere_encode_grad.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    ds = [vp, C.c_size_t, C.POINTER(DatasetGeom)]
+    L.te_dataset_layout.argtypes = [C.POINTER(DatasetGeom), C.POINTER(DatasetOffsets)]
+    L.te_dataset_init.argtypes = ds + [vp]
+    L.te_dataset_append.argtypes = ds + [i32] + [vp] * 6 + [vp]
+    L.te_dataset_gather.argtypes = ds + [i32, vp, u64, u64, i32, f32] + [vp] * 6 + [vp]
     if L.te_abi_version() != K.TE_ABI_VERSION:
         raise RuntimeError("libthreatengage.so ABI version differs from dronechase_amd.config")
     _LIB = L
@@ -156,7 +172,7 @@ def call(name: str, *args) -> None:
 
 def call_on(device, name: str, *args) -> None:
     """call() for the entries that act on the current device and take the stream last (te_policy_*, te_rollout_gae, te_adv_stats,
-    te_monitor_*): on `device`, on PyTorch's current stream of it."""
+    te_monitor_*, te_sphere_encode*, te_dataset_*): on `device`, on PyTorch's current stream of it."""
     import torch
     with torch.cuda.device(device):
         call(name, *args, torch.cuda.current_stream(device).cuda_stream)

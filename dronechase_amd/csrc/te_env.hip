@@ -53,6 +53,7 @@
 #include "te_policy_opt.hpp"
 #include "te_rollout.hpp"
 #include "te_monitor.hpp"
+#include "te_dataset.hpp"
 
 namespace te {
 
@@ -2475,6 +2476,92 @@ __attribute__((visibility("default"))) int te_monitor_stats(void* mon, size_t by
   if ((uintptr_t)out & 7) return fail("te_monitor_stats: out must be 8-byte aligned");
   hipLaunchKernelGGL(monitor_stats_kernel, dim3(1), dim3(kMonThreads), 0, (hipStream_t)stream, monitor_view(mon, n_envs, n_records), out,
                      (int)reset_window);
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- imitation dataset (te_dataset.hpp): every check is on the host, before any launch
+static int dataset_geom_check(const std::string& w, const te_dataset_geom* g) {
+  if (!g) return fail(w + ": null argument geom");
+  if (g->channels != 3) return fail(w + ": channels must be 3, not " + std::to_string(g->channels));
+  if (g->n_spheres < 1 || g->n_spheres > 8) return fail(w + ": n_spheres must be in 1 .. 8, not " + std::to_string(g->n_spheres));
+  if (g->capacity < 1) return fail(w + ": capacity must be in 1 .. 2^31 - 1, not " + std::to_string(g->capacity));
+  if (g->max_append_rows < 1 || g->max_append_rows > g->capacity)
+    return fail(w + ": max_append_rows must be in 1 .. capacity (" + std::to_string(g->capacity) + "), not " + std::to_string(g->max_append_rows));
+  return 0;
+}
+
+static int dataset_check(const std::string& w, const void* ds, size_t bytes, const te_dataset_geom* g) {
+  if (dataset_geom_check(w, g)) return 1;
+  if (!ds) return fail(w + ": null argument ds");
+  if ((uintptr_t)ds & 15) return fail(w + ": ds must be 16-byte aligned");
+  const size_t need = dataset_offsets(*g).bytes;
+  if (bytes < need) return fail(w + ": ds too small (bytes is " + std::to_string(bytes) + ", te_dataset_layout says " + std::to_string(need) + ")");
+  return 0;
+}
+
+struct DsPointer { const char* name; const void* p; unsigned align; };
+static int dataset_pointers_check(const std::string& w, std::initializer_list<DsPointer> ps) {
+  for (const DsPointer& q : ps) {
+    if (!q.p) return fail(w + ": null argument " + q.name);
+    if ((uintptr_t)q.p & (q.align - 1)) return fail(w + ": " + q.name + " must be " + std::to_string(q.align) + "-byte aligned");
+  }
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_dataset_layout(const te_dataset_geom* geom, te_dataset_offsets* out) {
+  const std::string who = "te_dataset_layout";
+  if (!out) return fail(who + ": null argument out");
+  if (dataset_geom_check(who, geom)) return 1;
+  *out = dataset_offsets(*geom);
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_dataset_init(void* ds, size_t bytes, const te_dataset_geom* geom, void* stream) {
+  if (dataset_check("te_dataset_init", ds, bytes, geom)) return 1;
+  TE_HIP(hipMemsetAsync(ds, 0, dataset_offsets(*geom).bytes, (hipStream_t)stream));
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_dataset_append(void* ds, size_t bytes, const te_dataset_geom* geom, int32_t n_rows,
+                                                             const float* stacked, const uint8_t* mask, const float* inertial,
+                                                             const float* last_action, const float* teacher, const uint8_t* active,
+                                                             void* stream) {
+  const std::string who = "te_dataset_append";
+  if (dataset_check(who, ds, bytes, geom)) return 1;
+  if (n_rows < 1 || n_rows > geom->max_append_rows)
+    return fail(who + ": n_rows must be in 1 .. max_append_rows (" + std::to_string(geom->max_append_rows) + "), not " + std::to_string(n_rows));
+  if (dataset_pointers_check(who, {{"stacked", stacked, 16}, {"mask", mask, 1}, {"inertial", inertial, 4}, {"last_action", last_action, 4},
+                                   {"teacher", teacher, 4}}))
+    return 1;
+  const DatasetView v = dataset_view(ds, *geom);
+  const hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(dataset_scan_kernel, dim3(1), dim3(kDsScanThreads), 0, s, v, mask, active, (int)n_rows);
+  TE_HIP(hipGetLastError());
+  hipLaunchKernelGGL(dataset_copy_kernel, dim3((unsigned)n_rows), dim3(kDsCopyThreads), 0, s, v, DatasetRows{stacked, mask, inertial, last_action, teacher});
+  TE_HIP(hipGetLastError());
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_dataset_gather(void* ds, size_t bytes, const te_dataset_geom* geom, int32_t batch,
+                                                             const int64_t* index, uint64_t seed, uint64_t draw, int32_t last_action_mode,
+                                                             float noise_std, float* out_stacked, uint8_t* out_mask, float* out_inertial,
+                                                             float* out_last_action, float* out_teacher, int64_t* out_index, void* stream) {
+  const std::string who = "te_dataset_gather";
+  if (dataset_check(who, ds, bytes, geom)) return 1;
+  if (batch < 1) return fail(who + ": batch must be >= 1, not " + std::to_string(batch));
+  if (last_action_mode < TE_DATASET_LA_KEEP || last_action_mode > TE_DATASET_LA_NOISE)
+    return fail(who + ": last_action_mode must be 0 (keep), 1 (random) or 2 (noise), not " + std::to_string(last_action_mode));
+  if (!(noise_std >= 0.f) || !std::isfinite(noise_std)) return fail(who + ": noise_std must be finite and >= 0");
+  if ((uintptr_t)index & 7) return fail(who + ": index must be 8-byte aligned");
+  if ((uintptr_t)out_index & 7) return fail(who + ": out_index must be 8-byte aligned");
+  if (dataset_pointers_check(who, {{"out_stacked", out_stacked, 16}, {"out_mask", out_mask, 1}, {"out_inertial", out_inertial, 4},
+                                   {"out_last_action", out_last_action, 4}, {"out_teacher", out_teacher, 4}}))
+    return 1;
+  const DatasetBatch b{out_stacked, out_mask, out_inertial, out_last_action, out_teacher, reinterpret_cast<long long*>(out_index),
+                       reinterpret_cast<const long long*>(index), (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)draw, (uint32_t)(draw >> 32),
+                       (int)last_action_mode, noise_std};
+  hipLaunchKernelGGL(dataset_gather_kernel, dim3((unsigned)batch), dim3(kDsCopyThreads), 0, (hipStream_t)stream, dataset_view(ds, *geom), b);
   TE_HIP(hipGetLastError());
   return 0;
 }

@@ -11,15 +11,20 @@ oddly padded convolutions over N x 6 small spheres, also exists as a pair of HIP
 te_sphere_encode_grad, csrc/te_sphere.hpp): StudentDriver(student, fused_encoder=True) runs inference through the first,
 fused_conv_stack / StudentTrainer(student, fused_encoder=True) train through both.
 
+The data between the collector and the trainer lives in imitation.ImitationDataset (a ring in device memory filled from
+BatchedEnv.step_students and sampled by HIP kernels); StudentTrainer.fit is the reference's training loop over it, kill_high_correlation
+included.
+
 Not here: bf16, a gradient with respect to the spheres, fusing Linear(1792, 512) / the DeepSet / trunk / heads, PPO on the stacked
-observation, an on-device dataset loop around step_students, kill_high_correlation, SB3 model.zip import of the MultiInputPolicy +
-FLIAExtractor form, and the reference file's unused CellGNN / AttentionPooling / SingleWorldView* classes."""
+observation, SB3 model.zip import of the MultiInputPolicy + FLIAExtractor form, and the reference file's unused CellGNN /
+AttentionPooling / SingleWorldView* classes."""
 from __future__ import annotations
 
 import ctypes as C
 from collections import OrderedDict
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -322,8 +327,8 @@ def fused_conv_stack(student: FLIAStudent, stacked: torch.Tensor, mask: Optional
 class StudentTrainer:
     """The reference's supervised step (sl_pipeline.py:172-207): Adam, loss_mae_direction with w_mag = 1, w_dir = 100,
     w_raw_direction = 60, and clip_grad_norm_(1.0).  step() works on tensors that already are on the student's device (e.g. the armed
-    rows of BatchedEnv.step_students) and makes no host read: the loss comes back as a tensor.  The reference's
-    kill_high_correlation (noise on / dropout of last_action before the step) is the caller's business and is not restated.
+    rows of BatchedEnv.step_students) and makes no host read: the loss comes back as a tensor.  fit() is the reference's loop of such
+    steps over an imitation.ImitationDataset, with its kill_high_correlation (noise on / replacement of last_action before the step).
 
     fused_encoder=True: the two conv blocks run through fused_conv_stack (te_sphere_encode forward, te_sphere_encode_grad backward;
     fp32 MFMA, the spheres the network does not look at skipped in both); Linear(1792, 512), the DeepSet, the trunk and the heads stay
@@ -342,6 +347,8 @@ class StudentTrainer:
             raise ValueError("StudentTrainer(fused_encoder=True) runs the HIP kernels te_sphere_encode and te_sphere_encode_grad: "
                              "the student must live on a GPU")
         self.optimizer = torch.optim.Adam(student.parameters(), lr=lr)
+        self.noise_seed, self.batches_fitted = 0, 0     # fit(): the key and the running draw of te_dataset_gather's last_action noise
+        self.last_modes: list = []                       # fit(): kill_high_correlation's branch of every batch of the last call
 
     def step(self, obs: Dict[str, torch.Tensor], teacher_action: torch.Tensor) -> torch.Tensor:
         self.student.train()
@@ -355,6 +362,46 @@ class StudentTrainer:
         nn.utils.clip_grad_norm_(self.student.parameters(), max_norm=1.0)
         self.optimizer.step()
         return loss.detach()
+
+    def fit(self, dataset, epochs: int = 1, batch_size: int = 1024, rng: Optional[np.random.Generator] = None,
+            kill_high_correlation: bool = True) -> torch.Tensor:
+        """_train_ppo's loop (sl_pipeline.py:172-207) over an imitation.ImitationDataset on the student's device.  Per epoch one
+        permutation of range(size) (torch.randperm on the device, PyTorch's device generator: torch.manual_seed fixes it) is stepped
+        through in batches of batch_size, the last short one kept.  Per batch p = rng.random() (a numpy Generator, default
+        default_rng(42)) picks kill_high_correlation's branch as the reference does: p < 0.2 replaces last_action by uniform noise,
+        p < 0.6 keeps it, anything else adds N(0, 0.2) noise and clamps; the noise itself is drawn on the device by
+        te_dataset_gather, keyed by (self.noise_seed, the ordinal of the batch among all this trainer has fitted), so rng is asked for
+        exactly one number per batch.  kill_high_correlation=False keeps last_action and draws nothing from rng.  The permutation addresses the ring's slots; after a wrap they are not in age order,
+        which a permutation does not care about.  Returns the per-batch losses [epochs * ceil(size / batch_size)] as one device
+        tensor; the only host read is the dataset's size, once."""
+        from .imitation import ImitationDataset, last_action_mode
+        if not isinstance(dataset, ImitationDataset):
+            raise ValueError("StudentTrainer.fit: dataset must be an imitation.ImitationDataset (a ring on a GPU), not "
+                             f"{type(dataset).__name__}")
+        device = next(self.student.parameters()).device
+        if dataset.device != device:
+            raise ValueError(f"StudentTrainer.fit: dataset lives on {dataset.device}, the student on {device}")
+        if dataset.n_spheres != self.student.n_spheres:
+            raise ValueError(f"StudentTrainer.fit: dataset has {dataset.n_spheres} spheres per row, the student takes {self.student.n_spheres}")
+        epochs, batch_size = int(epochs), int(batch_size)
+        if epochs < 1 or batch_size < 1:
+            raise ValueError("StudentTrainer.fit: epochs and batch_size must be >= 1")
+        size = dataset.size()
+        if size < 1:
+            raise ValueError("StudentTrainer.fit: dataset is empty")
+        rng = np.random.default_rng(42) if rng is None else rng
+        self.last_modes = []
+        losses = []
+        for _ in range(epochs):
+            perm = torch.randperm(size, device=device)
+            for at in range(0, size, batch_size):
+                index = perm[at:at + batch_size]
+                mode = last_action_mode(rng.random()) if kill_high_correlation else "keep"
+                self.last_modes.append(mode)
+                obs, teacher = dataset.batch(int(index.numel()), index=index, last_action_mode=mode, seed=self.noise_seed, draw=self.batches_fitted)
+                losses.append(self.step(obs, teacher))
+                self.batches_fitted += 1
+        return torch.stack(losses)
 
 
 class StudentDriver:

@@ -824,6 +824,67 @@ int te_sphere_encode_grad(const float* params, int32_t channels, int32_t n_rows,
                           const uint8_t* mask, const float* out, const float* d_out, float* grad, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* Imitation dataset: the middle of the reference's student line, between its collector (apps/threatsense_runner/collect_and_save.py:
+ * step Level5DumbMultiObs, drop the rows whose validity mask is all false, keep the rest) and its trainer
+ * (SupervisedImitationTrainer._train_ppo, core/rl_framework/utils/sl_pipeline.py:172-207, which perturbs last_action with
+ * kill_high_correlation before every batch).  A ring of student rows in device memory: te_dataset_append takes te_step_students'
+ * outputs as they are, te_dataset_gather writes the contiguous batch tensors te_sphere_encode and the student read.  A row
+ * (24 434 bytes at 6 spheres) never leaves HBM.  dronechase_amd/csrc/te_dataset.hpp.
+ *
+ * A dataset is ONE caller-owned device buffer of te_dataset_layout(geom)->bytes bytes, 16-byte aligned.  The calls take no te_env,
+ * allocate nothing, enqueue on `stream` of the current device only (no host synchronisation: a HIP graph can capture them), and
+ * every call takes the (ds, bytes, geom) the buffer was initialised with.  Served: channels == 3, 1 <= n_spheres <= 8,
+ * 1 <= max_append_rows <= capacity <= 2^31 - 1.  Any other value, a NULL, misaligned or short buffer, and the argument errors named
+ * below are refused with te_last_error text that names the argument, before anything is launched.
+ *
+ * Buffer layout (byte offsets from te_dataset_layout, a host-only call; every array 16-byte aligned, in this order, nothing
+ * overlaps): header (64 bytes; word 0 = total, i64, the number of rows ever appended; the rest reserved and zero);
+ * dst [max_append_rows] i32 (scratch of one append); the rings stacked [capacity][S][3][13][26] f32, mask [capacity][S] u8,
+ * inertial [capacity][15] f32, last_action [capacity][4] f32, teacher [capacity][4] f32.  size = min(total, capacity); the k-th kept
+ * row of an append that found total = T lands in slot (T + k) mod capacity.  te_dataset_init zeroes the whole buffer.
+ *
+ * te_dataset_append: stacked [n_rows][S][3][13][26] f32 (16-byte aligned), mask [n_rows][S] u8, inertial [n_rows][15] f32,
+ * last_action and teacher [n_rows][4] f32 (teacher may alias last_action), active [n_rows] u8 or NULL (every row active): exactly
+ * te_step_students' outputs with n_rows = N * P.  1 <= n_rows <= max_append_rows.  A row is KEPT iff it is active and any of its mask
+ * bytes is non-zero (the collector's armed rows behind drop_invalid_student_obs).  Kept rows are appended in source-row order and
+ * total advances by their count, on the device.  Of a row that is not kept only active and mask are read: the rest may hold NaN.  The
+ * inputs must not overlap the dataset.  Two launches: a scan (one workgroup; keep flags and their exclusive prefix sum in row order
+ * -> dst[row] = slot or -1, and the new total) and a copy (one workgroup per source row, 16-byte loads and stores).  No workgroup
+ * waits on another.
+ *
+ * te_dataset_gather: one launch, one workgroup per output row, into out_stacked [batch][S][3][13][26] f32 (16-byte aligned),
+ * out_mask [batch][S] u8, out_inertial [batch][15] f32, out_last_action and out_teacher [batch][4] f32, and, when not NULL,
+ * out_index [batch] i64 (the slots used).  batch >= 1.  index (i64 [batch], DEVICE memory, 8-byte aligned, or NULL) names the slots; a
+ * value outside [0, capacity) is clamped into it, so the call is memory-safe whatever index holds; staying below size is the
+ * caller's contract (a slot never written holds te_dataset_init's zeros).  With index == NULL row j draws its slot from the size the
+ * kernel reads on the device: slot_j = mulhi32(w.x, size), w = philox4x32_10(counter (j, draw_lo, draw_hi, 1), key (seed_lo, seed_hi));
+ * at size == 0 every output row is zeros and out_index is -1.
+ * last_action_mode is the branch of the reference's kill_high_correlation for this batch (the reference draws the branch once per
+ * batch, on the host).  With w = philox4x32_10((j, draw_lo, draw_hi, 2), key) and u(x) = x >> 8:
+ *   TE_DATASET_LA_KEEP    out_last_action = the stored row
+ *   TE_DATASET_LA_RANDOM  la[k] = (float)u(w[k]) * 2^-23 - 1: exact in fp32, in [-1, 1)
+ *   TE_DATASET_LA_NOISE   la[k] = clamp(la[k] + noise_std * z[k], -1, 1), z from two Box-Muller pairs: u1 = (u(w.x) + 1) * 2^-24,
+ *                         u2 = u(w.y) * 2^-24, r = sqrtf(-2 logf(u1)), z0 = r cosf(2 pi u2), z1 = r sinf(2 pi u2); z2, z3 the same from
+ *                         (w.z, w.w).  noise_std >= 0; the reference's alpha = 0.1 is noise_std = 0.2.
+ * stacked, mask, inertial and teacher are never perturbed.  The same arguments give the same bits on every call. */
+typedef struct te_dataset_geom {
+  int32_t capacity, max_append_rows, n_spheres, channels;
+} te_dataset_geom;
+
+typedef struct te_dataset_offsets {
+  size_t bytes, header, dst, stacked, mask, inertial, last_action, teacher;
+} te_dataset_offsets;
+
+enum { TE_DATASET_LA_KEEP = 0, TE_DATASET_LA_RANDOM = 1, TE_DATASET_LA_NOISE = 2 };
+
+int te_dataset_layout(const te_dataset_geom* geom, te_dataset_offsets* out);
+int te_dataset_init(void* ds, size_t bytes, const te_dataset_geom* geom, void* stream);
+int te_dataset_append(void* ds, size_t bytes, const te_dataset_geom* geom, int32_t n_rows, const float* stacked, const uint8_t* mask,
+                      const float* inertial, const float* last_action, const float* teacher, const uint8_t* active, void* stream);
+int te_dataset_gather(void* ds, size_t bytes, const te_dataset_geom* geom, int32_t batch, const int64_t* index, uint64_t seed,
+                      uint64_t draw, int32_t last_action_mode, float noise_std, float* out_stacked, uint8_t* out_mask,
+                      float* out_inertial, float* out_last_action, float* out_teacher, int64_t* out_index, void* stream);
+
 int te_abi_version(void);
 const char* te_last_error(void);
 
