@@ -26,6 +26,7 @@ EXPORTS = (
     "te_rollout_gae", "te_adv_stats_workspace_bytes", "te_adv_stats",
     "te_monitor_bytes", "te_monitor_layout", "te_monitor_init", "te_monitor_step", "te_monitor_stats",
     "te_sphere_encode_param_words", "te_sphere_encode", "te_sphere_encode_grad_workspace_bytes", "te_sphere_encode_grad",
+    "te_sphere_bf16_words", "te_sphere_pack_bf16", "te_sphere_encode_bf16",
     "te_dataset_layout", "te_dataset_init", "te_dataset_append", "te_dataset_gather",
 )
 
@@ -149,6 +150,9 @@ def load() -> C.CDLL:
     L.te_sphere_encode.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.te_sphere_encode_grad_workspace_bytes.argtypes = [i32, i32, i32, C.POINTER(C.c_size_t)]
     L.te_sphere_encode_grad.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.te_sphere_bf16_words.argtypes = [i32, C.POINTER(C.c_size_t)]
+    L.te_sphere_pack_bf16.argtypes = [vp, i32, vp, vp]
+    L.te_sphere_encode_bf16.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
     ds = [vp, C.c_size_t, C.POINTER(DatasetGeom)]
     L.te_dataset_layout.argtypes = [C.POINTER(DatasetGeom), C.POINTER(DatasetOffsets)]
     L.te_dataset_init.argtypes = ds + [vp]

@@ -47,6 +47,7 @@
 #include "te_policy.hpp"
 #include "te_policy_bf16.hpp"
 #include "te_sphere.hpp"
+#include "te_sphere_bf16.hpp"
 #include "te_wingman.hpp"
 #include "te_policy_grad.hpp"
 #include "te_policy_grad_bf16.hpp"
@@ -2232,6 +2233,37 @@ __attribute__((visibility("default"))) int te_sphere_encode(const float* params,
   const int total = n_rows * n_spheres;
   const SphereIO io{params, stacked, mask, out, n_spheres, total};
   return policy_launch(&sphere_encode_kernel<3>, PolGeom{1, kSphThreads, sph_lds_plan(3).words * 4}, std::min(total, n_cu), stream, io);
+}
+
+// te_sphere_encode with bf16 operands (te_sphere_bf16.hpp): the packed bf16 copy of the two conv weights, and the launch
+__attribute__((visibility("default"))) int te_sphere_bf16_words(int32_t channels, size_t* out_halfwords) {
+  if (!out_halfwords) return fail("te_sphere_bf16_words: null argument out_halfwords");
+  if (sphere_channels_check("te_sphere_bf16_words", channels)) return 1;
+  *out_halfwords = (size_t)sph_bf16_layout().words;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int te_sphere_pack_bf16(const float* params, int32_t channels, uint16_t* out, void* stream) {
+  const std::string who = "te_sphere_pack_bf16";
+  if (sphere_channels_check(who, channels)) return 1;
+  if (sphere_pointers_check(who, {{"params", params}, {"out", out}})) return 1;
+  const int words = sph_bf16_layout().words;
+  return policy_launch(&sphere_pack_bf16_kernel, PolGeom{256, 256, 0}, words, stream, params, reinterpret_cast<__bf16*>(out));
+}
+
+__attribute__((visibility("default"))) int te_sphere_encode_bf16(const float* params, const uint16_t* weights_bf16, int32_t channels,
+                                                                 int32_t n_rows, int32_t n_spheres, const float* stacked,
+                                                                 const uint8_t* mask, float* out, void* stream) {
+  const std::string who = "te_sphere_encode_bf16";
+  if (sphere_domain_check(who, channels, n_rows, n_spheres)) return 1;
+  if (sphere_pointers_check(who, {{"params", params}, {"weights_bf16", weights_bf16}, {"stacked", stacked}, {"out", out}})) return 1;
+  // persistent workgroups, two per CU at most: each holds its weight fragments in registers and strides over the spheres
+  int n_cu = 0;
+  if (sphere_cu_count(who, &n_cu)) return 1;
+  const int total = n_rows * n_spheres;
+  const SphereIO io{params, stacked, mask, out, n_spheres, total};
+  return policy_launch(&sphere_encode_bf16_kernel<3>, PolGeom{1, kSphThreads, 0}, (int)std::min<int64_t>(total, (int64_t)kSphBGroupsPerCu * n_cu), stream,
+                       io, weights_bf16);
 }
 
 // The workspace of te_sphere_encode_grad: one partial gradient per workgroup the call can launch.  The bound on the grid does not

@@ -9,13 +9,16 @@ and shapes are pinned from the reference module itself (tests/golden/student_fli
 Everything is a PyTorch module of this package, trainable with autograd.  The one part PyTorch handles badly, the sphere CNN's two
 oddly padded convolutions over N x 6 small spheres, also exists as a pair of HIP kernels (te_sphere_encode and its parameter gradient
 te_sphere_encode_grad, csrc/te_sphere.hpp): StudentDriver(student, fused_encoder=True) runs inference through the first,
-fused_conv_stack / StudentTrainer(student, fused_encoder=True) train through both.
+fused_conv_stack / StudentTrainer(student, fused_encoder=True) train through both.  The forward also exists with bf16 operands on the
+bf16 MFMA (te_sphere_encode_bf16, csrc/te_sphere_bf16.hpp): StudentDriver(student, fused_encoder=True, encoder_precision="bf16"), for
+inference only.
 
 The data between the collector and the trainer lives in imitation.ImitationDataset (a ring in device memory filled from
 BatchedEnv.step_students and sampled by HIP kernels); StudentTrainer.fit is the reference's training loop over it, kill_high_correlation
 included.
 
-Not here: bf16, a gradient with respect to the spheres, fusing Linear(1792, 512) / the DeepSet / trunk / heads, PPO on the stacked
+Not here: bf16 in training (a bf16 forward needs a backward of the same forward) or behind the encoder, a gradient with respect to
+the spheres, fusing Linear(1792, 512) / the DeepSet / trunk / heads, PPO on the stacked
 observation, SB3 model.zip import of the MultiInputPolicy + FLIAExtractor form, and the reference file's unused CellGNN /
 AttentionPooling / SingleWorldView* classes."""
 from __future__ import annotations
@@ -416,14 +419,28 @@ class StudentDriver:
     blocks, and less with a rollout's masks (profiles/student_encode.json): it was not slower at any size measured.
     At 65 536 rows the PyTorch formulation's one call also differed from its own result computed 8 192 rows at a time (by up to 1.09; its
     intermediates are past 2^31 bytes there), which the launch did not: fly batches of that size through the fused encoder.
-    The switch is opt-in because the default must run wherever the module does (a CPU, autograd)."""
-    accepts_torch = True
+    The switch is opt-in because the default must run wherever the module does (a CPU, autograd).
 
-    def __init__(self, student: FLIAStudent, fused_encoder: bool = False):
+    encoder_precision="bf16" (with fused_encoder=True; the default is "fp32"): the launch is te_sphere_encode_bf16, the same two blocks
+    with bf16 operands on the bf16 MFMA under the contract of include/threatengage.h: conv weights, cells and block1's output rounded to
+    bf16 (round-to-nearest-even), fp32 accumulation from the fp32 bias, fp32 output in the same buffer, so everything behind the
+    encoder is unchanged.  The driver owns a second buffer with the bf16 weights, which keeps its address too; refresh() repacks both.
+    The features differ from the fp32 launch's by bf16 rounding (DESIGN.md section 7 has the measured gaps and timings,
+    profiles/student_encode_bf16.json the run).  Opt-in because it changes the numbers."""
+    accepts_torch = True
+    PRECISIONS = ("fp32", "bf16")
+
+    def __init__(self, student: FLIAStudent, fused_encoder: bool = False, encoder_precision: str = "fp32"):
         if not isinstance(student, FLIAStudent):
             raise TypeError("StudentDriver: student must be a FLIAStudent")
+        if encoder_precision not in self.PRECISIONS:
+            raise ValueError(f"StudentDriver: encoder_precision must be one of {self.PRECISIONS}, not {encoder_precision!r}")
+        if encoder_precision == "bf16" and not fused_encoder:
+            raise ValueError("StudentDriver: encoder_precision='bf16' is the HIP kernel te_sphere_encode_bf16 and needs fused_encoder=True; "
+                             "the PyTorch formulation has no bf16 form")
         self.student = student
         self.fused_encoder = bool(fused_encoder)
+        self.encoder_precision = encoder_precision
         self.low = None
         if self.fused_encoder:
             self.device = next(student.parameters()).device
@@ -434,6 +451,10 @@ class StudentDriver:
             if sum(p.numel() for p in self._conv_tensors()) != words.value:
                 raise ValueError("StudentDriver: the student's conv blocks do not have te_sphere_encode's layout")
             self.params = torch.empty(int(words.value), dtype=torch.float32, device=self.device)
+            self.weights_bf16 = None
+            if self.encoder_precision == "bf16":
+                _lib.call("te_sphere_bf16_words", student.lidar_shape[0], C.byref(words))
+                self.weights_bf16 = torch.empty(int(words.value), dtype=torch.int16, device=self.device)   # bf16 bit patterns
             self._out = None
             self.refresh()
 
@@ -445,10 +466,13 @@ class StudentDriver:
     def refresh(self) -> None:
         if self.fused_encoder:
             torch.cat([p.detach().reshape(-1) for p in self._conv_tensors()], out=self.params)
+            if self.weights_bf16 is not None:
+                _lib.call_on(self.device, "te_sphere_pack_bf16", self.params.data_ptr(), self.student.lidar_shape[0], self.weights_bf16.data_ptr())
 
     def encode(self, stacked: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
-        """te_sphere_encode: stacked [B, N, 3, 13, 26] f32, mask [B, N] uint8 / bool or None (every sphere counts) ->
-        [B, N, 1792]; a buffer of this object, overwritten by the next call of the same batch size."""
+        """te_sphere_encode (te_sphere_encode_bf16 with encoder_precision="bf16"): stacked [B, N, 3, 13, 26] f32, mask [B, N] uint8 /
+        bool or None (every sphere counts) -> [B, N, 1792] f32; a buffer of this object, overwritten by the next call of the same
+        batch size."""
         if not self.fused_encoder:
             raise ValueError("StudentDriver.encode: built with fused_encoder=False")
         B, N = int(stacked.shape[0]), int(stacked.shape[1])
@@ -460,8 +484,12 @@ class StudentDriver:
                 mask = mask.view(torch.uint8)
         if self._out is None or self._out.shape[:2] != (B, N):
             self._out = torch.empty((B, N, SPHERE_FEATURES), dtype=torch.float32, device=self.device)
-        _lib.call_on(self.device, "te_sphere_encode", self.params.data_ptr(), self.student.lidar_shape[0], B, N, stacked.data_ptr(),
-                     _lib._ptr(mask), self._out.data_ptr())
+        if self.weights_bf16 is not None:
+            _lib.call_on(self.device, "te_sphere_encode_bf16", self.params.data_ptr(), self.weights_bf16.data_ptr(), self.student.lidar_shape[0],
+                         B, N, stacked.data_ptr(), _lib._ptr(mask), self._out.data_ptr())
+        else:
+            _lib.call_on(self.device, "te_sphere_encode", self.params.data_ptr(), self.student.lidar_shape[0], B, N, stacked.data_ptr(),
+                         _lib._ptr(mask), self._out.data_ptr())
         return self._out
 
     @torch.no_grad()

@@ -802,6 +802,36 @@ int te_sphere_encode_param_words(int32_t channels, size_t* out_words);
 int te_sphere_encode(const float* params, int32_t channels, int32_t n_rows, int32_t n_spheres, const float* stacked,
                      const uint8_t* mask, float* out, void* stream);
 
+/* te_sphere_encode with bf16 operands on the bf16 MFMA (v_mfma_f32_16x16x32_bf16), opt-in, inference only
+ * (dronechase_amd/csrc/te_sphere_bf16.hpp).  The same function, arguments, counting rule, output type and layout.  Numerics contract:
+ *   - both conv weights are rounded once to bf16, round-to-nearest-even, by te_sphere_pack_bf16; the fp32 parameter buffer stays the
+ *     master copy, and both biases are read from it in fp32;
+ *   - a sphere's cells are rounded to bf16 (round-to-nearest-even) when they are staged for the MFMA; the padding constant 1.0 is exact;
+ *   - products are accumulated in fp32 by the MFMA, the accumulator starting from the fp32 bias; ReLU runs in fp32;
+ *   - block1's post-ReLU output is rounded to bf16 (round-to-nearest-even) where it is stored for block2;
+ *   - block2's output is stored as fp32: out is te_sphere_encode's buffer, so everything behind the encoder is unchanged;
+ *   - an element's sum order is over k only (k-blocks of 32 in order, within a block the MFMA's own order): a sphere's features are
+ *     bitwise the same in any row, slot, batch, grid or mask of other spheres, and repeated calls are bitwise equal;
+ *   - a sphere that does not count gets 1792 zeros and its input is never read.
+ * The output therefore differs from te_sphere_encode's by bf16 rounding (measured: README).
+ *
+ * weights_bf16 is ONE device buffer of te_sphere_bf16_words(channels) = 22 528 uint16 elements, 16-byte aligned, bf16 bit patterns,
+ * two tensors [N][Kp] row-major, each 16-byte aligned:
+ *   element 0:     conv1 [32][128], column k = (ci * 5 + kh) * 8 + kw holds w[n][ci][kh][kw]; the columns with kw >= 5 and the
+ *                  columns k >= 120 are zero (the kernel width is padded from 5 to 8);
+ *   element 4096:  conv2 [64][288], column k = (kh * 3 + kw) * 32 + ci holds w[n][ci][kh][kw].
+ * Biases are not in it.  te_sphere_pack_bf16 fills it from `params` (te_sphere_encode's buffer) in one launch on `stream`, no host
+ * synchronisation; call it again after every change of `params`.
+ *
+ * Served: te_sphere_encode's domain.  A value outside it, a NULL pointer other than mask, or params / weights_bf16 / out / stacked not
+ * 16-byte aligned is refused with te_last_error text that names the call and the argument, before anything is launched.  One launch
+ * on `stream` of the current device, no allocation and no host synchronisation.  There is no bf16 backward: train through
+ * te_sphere_encode and te_sphere_encode_grad. */
+int te_sphere_bf16_words(int32_t channels, size_t* out_halfwords);
+int te_sphere_pack_bf16(const float* params, int32_t channels, uint16_t* out, void* stream);
+int te_sphere_encode_bf16(const float* params, const uint16_t* weights_bf16, int32_t channels, int32_t n_rows, int32_t n_spheres,
+                          const float* stacked, const uint8_t* mask, float* out, void* stream);
+
 /* The backward of te_sphere_encode with respect to its parameters: grad (te_sphere_encode_param_words(channels) floats, in params'
  * layout) = sum over the counting spheres of d(out) / d(params) applied to d_out.  No gradient with respect to `stacked` exists: it is
  * an observation.
