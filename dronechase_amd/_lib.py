@@ -193,6 +193,14 @@ def require_f32(who: str, name: str, t, shape, device, shown=None) -> None:
         raise ValueError(f"{who}: {name} must be a contiguous float32 {shown or shape} tensor on {device}")
 
 
+def require_bytes(who: str, name: str, t, shape, device):
+    """A mask of the sphere encoder's and the dataset's ABI calls: contiguous uint8 or bool of `shape` on `device`; returns it as bytes."""
+    import torch
+    if tuple(t.shape) != tuple(shape) or t.dtype not in (torch.uint8, torch.bool) or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous uint8 or bool {list(shape)} tensor on {device}")
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
 def require_index(who: str, index, device) -> None:
     """The minibatch index of te_policy_ppo_grad and te_adv_stats: None (every row), or contiguous 1-D int64 on `device`."""
     import torch

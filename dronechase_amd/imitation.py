@@ -87,15 +87,10 @@ class ImitationDataset:
         _lib.require_f32(who, "inertial_data", obs["inertial_data"], (M, K.OBS_INERTIAL_WORDS), self.device)
         _lib.require_f32(who, "last_action", obs["last_action"], (M, 4), self.device)
         _lib.require_f32(who, "teacher", teacher, (M, 4), self.device)
-        mask = self._bytes(who, "validity_mask", obs["validity_mask"], (M, S))
+        mask = _lib.require_bytes(who, "validity_mask", obs["validity_mask"], (M, S), self.device)
         if active is not None:
-            active = self._bytes(who, "active", active, (M,))
+            active = _lib.require_bytes(who, "active", active, (M,), self.device)
         return M, obs["stacked_spheres"], mask, obs["inertial_data"], obs["last_action"], teacher, active
-
-    def _bytes(self, who: str, name: str, t: torch.Tensor, shape) -> torch.Tensor:
-        if tuple(t.shape) != tuple(shape) or t.dtype not in (torch.uint8, torch.bool) or t.device != self.device or not t.is_contiguous():
-            raise ValueError(f"{who}: {name} must be a contiguous uint8 or bool {list(shape)} tensor on {self.device}")
-        return t.view(torch.uint8) if t.dtype == torch.bool else t
 
     # ------------------------------------------------------------------ filling
     def clear(self) -> None:

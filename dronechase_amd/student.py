@@ -245,13 +245,23 @@ def _conv_tensors(student: FLIAStudent):
     return [cnn.block1[0].conv.weight, cnn.block1[0].conv.bias, cnn.block2[0].conv.weight, cnn.block2[0].conv.bias]
 
 
-def _mask_bytes(who: str, mask: Optional[torch.Tensor], B: int, N: int, device) -> Optional[torch.Tensor]:
-    """The validity mask as te_sphere_encode reads it: None, or contiguous uint8 / bool [B, N] on `device` (bool as its bytes)."""
-    if mask is None:
-        return None
-    if tuple(mask.shape) != (B, N) or mask.dtype not in (torch.uint8, torch.bool) or mask.device != device or not mask.is_contiguous():
-        raise ValueError(f"{who}: validity_mask must be a contiguous uint8 or bool [{B}, {N}] tensor on {device}")
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+def _conv_layout_words(who: str, student: FLIAStudent) -> int:
+    """te_sphere_encode's parameter count, which the student's two conv blocks must have."""
+    words = C.c_size_t()
+    _lib.call("te_sphere_encode_param_words", student.lidar_shape[0], C.byref(words))
+    if sum(p.numel() for p in _conv_tensors(student)) != words.value:
+        raise ValueError(f"{who}: the student's conv blocks do not have te_sphere_encode's layout")
+    return int(words.value)
+
+
+def _sphere_encode(params, weights_bf16, stacked, mask, out) -> None:
+    """The forward launch over stacked [B, N, C, 13, 26] into out: te_sphere_encode, or te_sphere_encode_bf16 when bf16 weights are given."""
+    B, N, channels = (int(v) for v in stacked.shape[:3])
+    if weights_bf16 is not None:
+        _lib.call_on(stacked.device, "te_sphere_encode_bf16", params.data_ptr(), weights_bf16.data_ptr(), channels, B, N, stacked.data_ptr(),
+                     _lib._ptr(mask), out.data_ptr())
+    else:
+        _lib.call_on(stacked.device, "te_sphere_encode", params.data_ptr(), channels, B, N, stacked.data_ptr(), _lib._ptr(mask), out.data_ptr())
 
 
 # te_sphere_encode_grad's workspaces, (device, stream, B, N) -> buffer, most recently used last.  A workspace is scratch of one call, so
@@ -282,8 +292,7 @@ class _FusedConvStack(torch.autograd.Function):
     def forward(ctx, params, stacked, mask):
         B, N = int(stacked.shape[0]), int(stacked.shape[1])
         out = torch.empty((B, N, SPHERE_FEATURES), dtype=torch.float32, device=stacked.device)
-        _lib.call_on(stacked.device, "te_sphere_encode", params.data_ptr(), int(stacked.shape[2]), B, N, stacked.data_ptr(), _lib._ptr(mask),
-                     out.data_ptr())
+        _sphere_encode(params, None, stacked, mask, out)
         ctx.save_for_backward(params, stacked, mask, out)
         return out
 
@@ -312,17 +321,15 @@ def fused_conv_stack(student: FLIAStudent, stacked: torch.Tensor, mask: Optional
     conv = _conv_tensors(student)
     if any(p.dtype != torch.float32 for p in conv):
         raise ValueError(f"fused_conv_stack: the student's conv tensors must be float32, not {conv[0].dtype}: the kernels read floats")
-    words = C.c_size_t()
-    _lib.call("te_sphere_encode_param_words", student.lidar_shape[0], C.byref(words))
-    if sum(p.numel() for p in conv) != words.value:
-        raise ValueError("fused_conv_stack: the student's conv blocks do not have te_sphere_encode's layout")
+    _conv_layout_words("fused_conv_stack", student)
     device = next(student.parameters()).device
     if device.type != "cuda" or stacked.device.type != "cuda":
         raise ValueError("fused_conv_stack runs the HIP kernels te_sphere_encode and te_sphere_encode_grad: the student and its "
                          "observation must live on a GPU")
     B, N = int(stacked.shape[0]), int(stacked.shape[1])
     _lib.require_f32("fused_conv_stack", "stacked_spheres", stacked, (B, N, *student.lidar_shape), device)
-    mask = _mask_bytes("fused_conv_stack", mask, B, N, device)
+    if mask is not None:
+        mask = _lib.require_bytes("fused_conv_stack", "validity_mask", mask, (B, N), device)
     params = torch.cat([p.reshape(-1) for p in conv])
     return _FusedConvStack.apply(params, stacked.detach(), mask)
 
@@ -446,26 +453,19 @@ class StudentDriver:
             self.device = next(student.parameters()).device
             if self.device.type != "cuda":
                 raise ValueError("StudentDriver(fused_encoder=True) runs the HIP kernel te_sphere_encode: the student must live on a GPU")
-            words = C.c_size_t()
-            _lib.call("te_sphere_encode_param_words", student.lidar_shape[0], C.byref(words))
-            if sum(p.numel() for p in self._conv_tensors()) != words.value:
-                raise ValueError("StudentDriver: the student's conv blocks do not have te_sphere_encode's layout")
-            self.params = torch.empty(int(words.value), dtype=torch.float32, device=self.device)
+            self.params = torch.empty(_conv_layout_words("StudentDriver", student), dtype=torch.float32, device=self.device)
             self.weights_bf16 = None
             if self.encoder_precision == "bf16":
+                words = C.c_size_t()
                 _lib.call("te_sphere_bf16_words", student.lidar_shape[0], C.byref(words))
                 self.weights_bf16 = torch.empty(int(words.value), dtype=torch.int16, device=self.device)   # bf16 bit patterns
             self._out = None
             self.refresh()
 
-    def _conv_tensors(self):
-        cnn = self.student.sphere_cnn
-        return [cnn.block1[0].conv.weight, cnn.block1[0].conv.bias, cnn.block2[0].conv.weight, cnn.block2[0].conv.bias]
-
     @torch.no_grad()
     def refresh(self) -> None:
         if self.fused_encoder:
-            torch.cat([p.detach().reshape(-1) for p in self._conv_tensors()], out=self.params)
+            torch.cat([p.detach().reshape(-1) for p in _conv_tensors(self.student)], out=self.params)
             if self.weights_bf16 is not None:
                 _lib.call_on(self.device, "te_sphere_pack_bf16", self.params.data_ptr(), self.student.lidar_shape[0], self.weights_bf16.data_ptr())
 
@@ -478,18 +478,10 @@ class StudentDriver:
         B, N = int(stacked.shape[0]), int(stacked.shape[1])
         _lib.require_f32("StudentDriver.encode", "stacked_spheres", stacked, (B, N, *self.student.lidar_shape), self.device)
         if mask is not None:
-            if tuple(mask.shape) != (B, N) or mask.dtype not in (torch.uint8, torch.bool) or mask.device != self.device or not mask.is_contiguous():
-                raise ValueError(f"StudentDriver.encode: validity_mask must be a contiguous uint8 or bool [{B}, {N}] tensor on {self.device}")
-            if mask.dtype == torch.bool:
-                mask = mask.view(torch.uint8)
+            mask = _lib.require_bytes("StudentDriver.encode", "validity_mask", mask, (B, N), self.device)
         if self._out is None or self._out.shape[:2] != (B, N):
             self._out = torch.empty((B, N, SPHERE_FEATURES), dtype=torch.float32, device=self.device)
-        if self.weights_bf16 is not None:
-            _lib.call_on(self.device, "te_sphere_encode_bf16", self.params.data_ptr(), self.weights_bf16.data_ptr(), self.student.lidar_shape[0],
-                         B, N, stacked.data_ptr(), _lib._ptr(mask), self._out.data_ptr())
-        else:
-            _lib.call_on(self.device, "te_sphere_encode", self.params.data_ptr(), self.student.lidar_shape[0], B, N, stacked.data_ptr(),
-                         _lib._ptr(mask), self._out.data_ptr())
+        _sphere_encode(self.params, self.weights_bf16, stacked, mask, self._out)
         return self._out
 
     @torch.no_grad()

@@ -112,9 +112,10 @@ def test_every_source_of_the_library_is_a_build_dependency(lib):
     csrc/ and include/ is a dependency, and touching any of them makes needs_build() true."""
     from dronechase_amd import build as B
     names = {os.path.basename(d) for d in B.deps()}
-    assert {"te_env.hip", "te_config.c", "te_device.hpp", "te_logic.hpp", "te_stacked.hpp", "threatengage.h"} <= names
+    assert {"te_env.hip", "te_config.c", "te_device.hpp", "te_logic.hpp", "te_stacked.hpp", "threatengage.h", "te_host.hpp", "te_policy_host.hpp",
+            "te_abi_stateless.hpp"} <= names
     # every quoted include of the HIP translation unit is covered
-    for src in ("te_env.hip", "te_logic.hpp", "te_stacked.hpp", "te_device.hpp"):
+    for src in ("te_env.hip", "te_logic.hpp", "te_stacked.hpp", "te_device.hpp", "te_host.hpp", "te_policy_host.hpp", "te_abi_stateless.hpp"):
         for inc in re.findall(r'#include "([^"]+)"', open(os.path.join(B.CSRC, src)).read()):
             assert os.path.basename(inc) in names, (src, inc)
     assert not B.needs_build()
